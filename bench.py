@@ -1,22 +1,31 @@
 """Benchmark: MST edges processed/sec on R-MAT (BASELINE.json metric) + % HBM roofline.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--scale S] [--workload rmat|grid|grid-gradient]
+                    [--dump-outputs DIR] [--full]
 
 A step = one full MST of the device-resident canonical edge list (BASELINE.md "Definitions"):
 validation, the weight-level plan, every level's pass and all Boruvka rounds -> in_mst flags +
 total weight. Inputs are generated on the GPU before the timed region (synthetic R-MAT, Graph500
 parameters, unique hashed weights — no dataset download).
-  N = 1: R-MAT scale 24 (BASELINE config 3), the headline `value`; the line also carries
-         `scaling_base`: R-MAT scale 26 (config 4's graph) solved on this one GPU.
+  N = 1: R-MAT scale 24 (BASELINE config 3), the headline `value`; with --full the line also
+         carries `scaling_base`: R-MAT scale 26 (config 4's graph) solved on this one GPU.
   N > 1 (torch.distributed.run, one rank per GPU, RCCL): strong scaling on R-MAT scale 26 —
          every N solves the same graph, so scaling_base and the N > 1 lines form one curve; a
          step there also gathers the MSF edge ids to rank 0 (the reference's collect_results),
-         ms_per_step_solve times the solve alone. "scaling" is "strong" on every line.
+         ms_per_step_solve (--full) times the solve alone. "scaling" is "strong" on every line.
 Input form (--input, config.input): at N = 1 on graphs with m >= 4n the canonical list is resident in
 both forms — CSR row offsets (the north_star's "CSR edge list in HBM", built on the device from the
 sorted u before the timed region, config.csr_offsets_build_ms) next to u, v, w: k_select streams
 the CSR form, k_filter the COO form; elsewhere COO (u, v, w).
-Rank 0 prints ONE JSON line. After the timed steps one extra step runs with every kernel launch
+Rank 0 prints ONE JSON line. A plain run does what the headline needs and no more: generate,
+set up, warm up, time --steps steps (`value` = m x steps / their wall time, `ms_per_step`), write
+the outputs when --dump-outputs DIR is given, print the line; everything below is null in it.
+--dump-outputs DIR: what the last timed step computed, as DIR/<name>.npy (dump_outputs below):
+the MSF totals, the in_mst flags counted per block of 4096 edges, and the flags at a fixed, seeded
+sample of edge ids. The inputs are generated from fixed seeds, so two builds run with the same
+arguments write comparable files.
+--full adds every other measurement and check, each with runs of its own after the timed steps.
+One extra step runs with every kernel launch
 bracketed by HIP events on the solve's stream (libghs_mst.so ghs_profile_enable): `kernels` lists
 every kernel's time per step and achieved GB/s under its algorithmic byte model (launch_bytes),
 `roofline` is the dominant kernel's (largest time in that step; k_select / k_filter durations are
@@ -24,11 +33,12 @@ the event averages inside the timed steps), `stage1_roofline` is BASELINE.md's s
 (24 B per live edge over every min-edge round / the min-edge kernels' time). `traffic` comes from
 the committed PMC profile (profiles/**/<workload>_pmc.json: rocprofv3 FETCH_SIZE / WRITE_SIZE
 passes, tools/gpu/pmc_traffic.sh) when one exists, else null.
-CPU baselines, rank 0 at N=1 only: `cpu_baseline` = the all-cores OpenMP Borůvka
+CPU baselines (--full), rank 0 at N=1 only: `cpu_baseline` = the all-cores OpenMP Borůvka
 (oracle/boruvka_omp.c, kind "port") on the workload's own graph with every CPU the process may
 use (affinity / cgroup quota / OMP_NUM_THREADS, reported under host_cpus); `cpu_baseline_serial`
 = the oracle's C Kruskal (1 thread) on R-MAT s22; `cpu_baseline_networkx` = NetworkX Kruskal (the
-reference's verifier) on R-MAT s16.
+reference's verifier) on R-MAT s16. At N > 1 --full also solves the graph on rank 0 alone first
+and compares the N-rank MSF with it edge for edge (`parity`).
 """
 import argparse
 import glob
@@ -58,15 +68,21 @@ def parse():
                     help="the device-resident input form: CSR (row offsets + v + w, ghs_mst_device_csr, ABI 9), "
                          "COO (u + v + w, ghs_mst_device) or both (offsets + u + v + w: k_select streams the "
                          "CSR form, k_filter the COO form); auto = both at N = 1, COO at N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the profiled step (kernels, rooflines), the CPU baselines, "
+                         "the host-path timing and the s26 scaling point; at N>1 the one-GPU parity check and the "
+                         "solve-only timing")
     ap.add_argument("--cpu-scale", type=int, default=22, help="R-MAT scale of the serial-Kruskal sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines and the host path")
     ap.add_argument("--nx-scale", type=int, default=16, help="R-MAT scale of the NetworkX baseline sample")
     ap.add_argument("--verify", action="store_true", help="check the result against the oracle (slow at s24)")
     ap.add_argument("--stats", action="store_true", help="print per-round stats to stderr")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend for N>1 (nccl = RCCL; gloo only to rehearse ranks sharing a GPU)")
     ap.add_argument("--verify-ranks", action="store_true", help="N>1: check every rank holds the same MSF")
-    ap.add_argument("--no-scaling-base", action="store_true", help="N=1: skip the s26 strong-scaling point")
+    ap.add_argument("--no-scaling-base", action="store_true", help="--full at N=1: skip the s26 strong-scaling point")
     ap.add_argument("--options", type=lambda x: int(x, 0), default=0,
                     help="ghs_config_t.options bits for N=1 (A/B of path options; 0 = the default path)")
     ap.add_argument("--level1", type=float, default=None, help="level plan: level-1 edges per vertex (default auto)")
@@ -75,7 +91,10 @@ def parse():
                     help="ghs_config_t.dedup_max for N=1 (parallel-edge filter at <= F fragments; A/B)")
     ap.add_argument("--coll-timeout", type=int, default=300,
                     help="N>1: seconds before a torch.distributed collective gives up (then every rank exits)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # Algorithmic bytes per launch of every profiled kernel (DESIGN.md "Kernels"): what the
@@ -561,6 +580,38 @@ def profile_step(step, n):
     return kernel_table(recs, stats, res, n), stage1_roofline(recs, stats), recs
 
 
+DUMP_BLOCK = 4096       # edges per entry of in_mst_block_counts
+DUMP_SAMPLE = 1 << 21   # flags in in_mst_sample (with the ids: 24 MiB, under the 64 MB a dump may take)
+DUMP_SEED = 20240607
+
+
+def dump_outputs(path, flags, res):
+    """What a caller of the timed path holds after a step, as <path>/<name>.npy: `flags` is the host
+    copy of the m in_mst flags (uint8, canonical edge order), `res` the step's Result.
+      mst_totals (float64, 3): MSF edges, total weight >> 32, total weight & 0xffffffff (a u64
+          weight does not fit a float64's 53 bits; both halves do)
+      in_mst_block_counts (float32, ceil(m / 4096)): flags set in every block of 4096 edges, so
+          every flag is covered
+      in_mst_sample_ids (float64), in_mst_sample (float32): min(m, 2^21) edge ids, ascending,
+          drawn without replacement by a fixed seed (all ids when m is smaller), and their flags"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    m = int(flags.size)
+    tw = int(res.total_weight)
+    np.save(os.path.join(path, "mst_totals.npy"),
+            np.array([int(res.num_mst_edges), tw >> 32, tw & 0xFFFFFFFF], dtype=np.float64))
+    padded = np.zeros(-(-m // DUMP_BLOCK) * DUMP_BLOCK, dtype=np.uint8)
+    padded[:m] = flags != 0
+    np.save(os.path.join(path, "in_mst_block_counts.npy"),
+            padded.reshape(-1, DUMP_BLOCK).sum(axis=1, dtype=np.uint32).astype(np.float32))
+    if m <= DUMP_SAMPLE:
+        ids = np.arange(m, dtype=np.int64)
+    else:
+        ids = np.sort(np.random.default_rng(DUMP_SEED).choice(m, size=DUMP_SAMPLE, replace=False))
+    np.save(os.path.join(path, "in_mst_sample_ids.npy"), ids.astype(np.float64))
+    np.save(os.path.join(path, "in_mst_sample.npy"), (flags[ids] != 0).astype(np.float32))
+
+
 def main():
     args = parse()
     if os.environ.get("GHS_BENCH_STACKS"):  # diagnostic: every rank's Python stacks every N seconds
@@ -621,7 +672,7 @@ def run(args, world, rank, dist, dev):
     cfg.update({"n": n, "m": m, "partition": f"canonical edge ranges x{world}", "parallelism": f"edges{world}"})
 
     ref = None
-    if world > 1:
+    if world > 1 and args.full:
         # the parity reference first, while no rank holds its engine: a one-GPU solve of the same
         # resident graph on rank 0 (its ~80 GB s26 workspace freed before the ranks allocate theirs)
         def reference():
@@ -648,22 +699,33 @@ def run(args, world, rank, dist, dev):
                         if custom else None)
     step = eng.run
     dt_solve = None
+    collected = [None]  # N > 1: the MSF edge ids the last step gathered (rank 0)
     if world > 1:
         # N > 1: a step ends with the MSF on rank 0, as the reference's MPI run ends with
         # collect_results (ghs_implementation_mpi.py:760-779): each rank's own-range MSF edge ids
-        # gathered to rank 0. The solve alone is timed separately (ms_per_step_solve).
-        dt_solve, _ = agreed("timed solves", lambda: time_steps(eng.run, args.steps, args.warmup, world, dist),
-                             rank, world, dist, dev)
+        # gathered to rank 0. --full times the solve alone separately (ms_per_step_solve).
+        if args.full:
+            dt_solve, _ = agreed("timed solves", lambda: time_steps(eng.run, args.steps, args.warmup, world, dist),
+                                 rank, world, dist, dev)
 
         def step():
             out = eng.run()
-            eng.collect_mst(0)
+            collected[0] = eng.collect_mst(0)
             return out
     dt, outs = agreed("timed steps", lambda: time_steps(step, args.steps, args.warmup, world, dist),
                       rank, world, dist, dev)
     results = [r for r, _ in outs]
     if len(set((r.total_weight, r.num_mst_edges) for r in results)) != 1:
         raise RuntimeError("non-deterministic MST across steps")
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        if world > 1:  # rank 0 holds the gathered MSF edge ids: back to flags over the m edges
+            flags = np.zeros(m, dtype=np.uint8)
+            flags[collected[0].cpu().numpy()] = 1
+        else:
+            flags = eng.in_mst[:m].cpu().numpy()
+        dump_outputs(args.dump_outputs, flags, results[-1])
+        del flags
     if world > 1 and args.verify_ranks:
         # every rank must hold the same MSF: (weight, edges, checksum of the chosen eids)
         flags = eng.gather_in_mst()
@@ -680,7 +742,7 @@ def run(args, world, rank, dist, dev):
                   file=sys.stderr)
 
     parity = None
-    if world > 1:
+    if world > 1 and args.full:
         # outside the timed steps: the N-rank MSF (gathered to rank 0) against the one-GPU reference,
         # edge for edge
         def check():
@@ -698,12 +760,14 @@ def run(args, world, rank, dist, dev):
 
         parity = agreed("parity vs the one-GPU solve", check, rank, world, dist, dev)
 
-    ktab, s1, _ = agreed("profiled step", lambda: profile_step(eng.run, n), rank, world, dist, dev)
+    ktab, s1 = None, None
+    if args.full:
+        ktab, s1, _ = agreed("profiled step", lambda: profile_step(eng.run, n), rank, world, dist, dev)
     # the canonical passes are also timed inside the timed steps (two events per pass, no idle
     # between dependent kernels of note): prefer those averages for k_select / k_filter
     for name, attr in (("k_select", "ms_select"), ("k_filter", "ms_filter")):
         ms = [getattr(r, attr) for r in results]
-        if name in ktab and ms and min(ms) > 0:
+        if ktab and name in ktab and ms and min(ms) > 0:
             t = ktab[name]
             t["ms"] = round(sum(ms) / len(ms) * t["launches"], 4)
             t["achieved_gbs"] = t["bytes"] / (t["ms"] * 1e-3) / 1e9
@@ -712,12 +776,15 @@ def run(args, world, rank, dist, dev):
     if rank == 0:
         ms_per_step = dt * 1e3 / args.steps
         value = m * args.steps / dt
-        with_bytes = {k: v for k, v in ktab.items() if v["bytes"] > 0}
-        dom = max(ktab, key=lambda k: ktab[k]["ms"])
-        if dom not in with_bytes:  # report the largest kernel that has a byte model
-            dom = max(with_bytes, key=lambda k: with_bytes[k]["ms"]) if with_bytes else None
-        roofline = roofline_obj(dom, ktab[dom], tag, "dominant kernel of the step (largest time in the profiled "
-                                "step among every launch; algorithmic bytes per DESIGN.md)") if dom else None
+        roofline = kernels = None
+        if ktab:
+            with_bytes = {k: v for k, v in ktab.items() if v["bytes"] > 0}
+            dom = max(ktab, key=lambda k: ktab[k]["ms"])
+            if dom not in with_bytes:  # report the largest kernel that has a byte model
+                dom = max(with_bytes, key=lambda k: with_bytes[k]["ms"]) if with_bytes else None
+            roofline = roofline_obj(dom, ktab[dom], tag, "dominant kernel of the step (largest time in the profiled "
+                                    "step among every launch; algorithmic bytes per DESIGN.md)") if dom else None
+            kernels = kernels_obj(ktab, tag)
         s0 = outs[-1][1]
         res0 = results[-1]
         breakdown = {
@@ -726,9 +793,8 @@ def run(args, world, rank, dist, dev):
             "per_round": [{"level": st["level"], "level_edges": st["level_arcs"], "live_edges": st["live_arcs"],
                            "fragments": st["active_components"], "hooks": st["hooks"]} for st in s0],
         }
-        kernels = kernels_obj(ktab, tag)
         cpu = cpu_omp = cpu_nx = e2e = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             e2e, g = end_to_end(edges, gen_s, res0)
             cpu_omp = cpu_baseline_omp(g, res0, tag)
             del g
@@ -736,7 +802,7 @@ def run(args, world, rank, dist, dev):
             cpu_nx = networkx_baseline(args.nx_scale, args.edgefactor)
         line = {"metric": METRIC, "value": round(value, 1), "unit": "edges/s", "n_gpus": world,
                 "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
-                "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+                "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "full": args.full,
                 "dtype": "u64", "data": "synthetic (generated on GPU)", "config": cfg, "roofline": roofline,
                 "stage1_roofline": s1, "cpu_baseline": cpu_omp, "cpu_baseline_serial": cpu,
                 "cpu_baseline_networkx": cpu_nx, "end_to_end": e2e, "kernels": kernels,
@@ -744,10 +810,10 @@ def run(args, world, rank, dist, dev):
         if world > 1:
             line["loop"] = loop
             line["parity"] = parity
-            line["ms_per_step_solve"] = round(dt_solve * 1e3 / args.steps, 4)
+            line["ms_per_step_solve"] = round(dt_solve * 1e3 / args.steps, 4) if dt_solve is not None else None
             line["step"] = "solve + gather of the MSF edge ids to rank 0 (collect_results)"
     del eng
-    if world == 1 and args.workload == "rmat" and args.scale is None and not args.no_scaling_base:
+    if args.full and world == 1 and args.workload == "rmat" and args.scale is None and not args.no_scaling_base:
         # the strong-scaling reference point: config 4's graph (R-MAT s26) on this one GPU, the
         # graph every N > 1 line of `bench.py --gpus N` solves
         del edges

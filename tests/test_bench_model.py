@@ -84,3 +84,39 @@ def test_stream_byte_model_per_form():
         bench.set_stream_forms(False, True, 1)
     assert bench._stream_bytes(_Cnt, n, "select") == 12.0 * 1000
     assert bench._pmc_match("k_select", "k_select<false>") and not bench._pmc_match("k_select", "k_select<true>")
+
+
+def test_dump_outputs_files(tmp_path):
+    """--dump-outputs: float32 / float64 arrays only; the block counts cover every flag, the sample
+    is the same edge ids on every call (fixed seed), and the u64 weight survives as two halves."""
+    import numpy as np
+
+    class _Out:
+        num_mst_edges = 0
+        total_weight = (1 << 55) + 12345  # past a float64's 53 bits
+
+    m = bench.DUMP_SAMPLE + 3 * bench.DUMP_BLOCK + 17  # sampled, and a last block that is not full
+    flags = (np.arange(m) % 7 == 0).astype(np.uint8)
+    flags[-1] = 1
+    _Out.num_mst_edges = int(flags.sum())
+    got = []
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), flags, _Out)
+        got.append({f[:-4]: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    a, b = got
+    assert sorted(a) == ["in_mst_block_counts", "in_mst_sample", "in_mst_sample_ids", "mst_totals"]
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 * 1000 * 1000
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    hi, lo = int(a["mst_totals"][1]), int(a["mst_totals"][2])
+    assert int(a["mst_totals"][0]) == _Out.num_mst_edges and (hi << 32) | lo == _Out.total_weight
+    counts = a["in_mst_block_counts"]
+    assert counts.size == -(-m // bench.DUMP_BLOCK) and counts.sum(dtype=np.float64) == flags.sum()
+    assert counts[-1] == flags[(counts.size - 1) * bench.DUMP_BLOCK:].sum()
+    ids = a["in_mst_sample_ids"].astype(np.int64)
+    assert ids.size == bench.DUMP_SAMPLE and np.all(np.diff(ids) > 0) and 0 <= ids[0] and ids[-1] < m
+    assert np.array_equal(a["in_mst_sample"], flags[ids].astype(np.float32))
+    # a list no longer than the sample is dumped whole, in order
+    bench.dump_outputs(str(tmp_path / "c"), flags[:1000], _Out)
+    assert np.array_equal(np.load(tmp_path / "c" / "in_mst_sample.npy"), flags[:1000].astype(np.float32))

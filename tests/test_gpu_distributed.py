@@ -59,7 +59,7 @@ def test_setup_failure_fails_every_rank(tmp_path):
 
 
 def test_bench_two_ranks_sharing_the_gpu(tmp_path):
-    """bench.py's N > 1 leg (gloo, both ranks on the one GPU, R-MAT s16): the line names the loop
+    """bench.py --full's N > 1 leg (gloo, both ranks on the one GPU, R-MAT s16): the line names the loop
     that ran and its MSF matches a one-GPU solve of the same graph edge for edge."""
     import torch
     if not torch.cuda.is_available():
@@ -68,7 +68,7 @@ def test_bench_two_ranks_sharing_the_gpu(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--scale", "16",
-           "--steps", "2", "--warmup", "1"]
+           "--steps", "2", "--warmup", "1", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])

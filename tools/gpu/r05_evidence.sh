@@ -8,10 +8,10 @@ OUT=gpurun_out/${TAG:-r05ev}
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 fatal() { case $1 in 124|134|137|139) echo "step '$2' ended with $1: stopping"; exit 1;; esac; }
-timeout -k 10 400 python3 -u bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"; rc=$?; fatal $rc bench-default
+timeout -k 10 400 python3 -u bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"; rc=$?; fatal $rc bench-default
 python3 -c "import json;d=json.load(open('$OUT/bench_default.json'));print('default value',round(d['value']/1e9,3),'ms',d['ms_per_step'],'s1',d['stage1_roofline']['frac'],'dom',d['roofline']['kernel'],d['roofline']['frac'],'cpu',d['cpu_baseline']['value'],'base',d.get('scaling_base',{}).get('ms_per_step'))" || tail -5 "$OUT/bench_default.err"
 for w in grid grid-gradient; do
-  timeout -k 10 300 python3 -u bench.py --workload $w --no-cpu-baseline --no-scaling-base > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err"; rc=$?; fatal $rc bench-$w
+  timeout -k 10 300 python3 -u bench.py --full --workload $w --no-cpu-baseline --no-scaling-base > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err"; rc=$?; fatal $rc bench-$w
   python3 -c "import json;d=json.load(open('$OUT/bench_$w.json'));print('$w value',round(d['value']/1e9,3),'ms',d['ms_per_step'],'s1',d['stage1_roofline']['frac'],'dom',d['roofline']['kernel'],d['roofline']['frac'])" || tail -5 "$OUT/bench_$w.err"
 done
 if [ -z "$NOTRACE" ]; then
