@@ -6,14 +6,15 @@ Entry points mirroring the reference:
   GHSAlgorithm(num_nodes, edges).run()      ghs_implementation.py:416-490
   python -m distributed_ghs_implementation_amd --graph-dir D
                                             ghs_implementation_mpi.py:884-954 (CLI)
-Array level: graph.canonicalize -> mst.minimum_spanning_forest; device level: device.DeviceMST;
-multi-GPU: distributed.DistributedMST.
+Array level: graph.canonicalize -> mst.minimum_spanning_forest (many small graphs in one launch:
+mst.minimum_spanning_forest_batch); device level: device.DeviceMST, device.batch_mst; multi-GPU:
+distributed.DistributedMST.
 """
 from .graph import (CanonicalGraph, canonicalize, read_graph_dir, read_mstbin, write_graph_dir, write_mstbin,
                     write_result)
-from .mst import GHSAlgorithm, MSTResult, minimum_spanning_forest
+from .mst import GHSAlgorithm, MSTResult, minimum_spanning_forest, minimum_spanning_forest_batch
 
 __all__ = [
     "CanonicalGraph", "canonicalize", "read_graph_dir", "read_mstbin", "write_graph_dir", "write_mstbin",
-    "write_result", "GHSAlgorithm", "MSTResult", "minimum_spanning_forest",
+    "write_result", "GHSAlgorithm", "MSTResult", "minimum_spanning_forest", "minimum_spanning_forest_batch",
 ]

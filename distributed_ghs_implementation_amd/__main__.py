@@ -13,6 +13,13 @@
     --check-result FILE
                    verify an existing result JSON against the graph; no GPU, no solve
 
+    --batch-dir ROOT
+                   many small graphs in one launch: every immediate subdirectory of ROOT holding
+                   graph_metadata.json or node_<id>.json files and every ROOT/*.mstbin is one graph
+                   (sorted order); writes each graph's ghs_mst.json next to its input and
+                   ROOT/ghs_experiments.json (the reference's experiment records); with --check the
+                   exit status is 1 if any record fails
+
     --gpus N       one process drives N GPUs of this node (RCCL clique, ghs_mst_multi)
     --generator {rmat,grid} --scale S --seed X
                    solve a synthetic BASELINE graph generated on the GPU instead of reading one
@@ -28,8 +35,71 @@ import sys
 import time
 
 
+def discover_batch(root):
+    """The graphs of a --batch-dir tree in sorted order: [(name, kind, path)] with kind "dir" (an
+    immediate subdirectory holding graph_metadata.json or node_<id>.json files) or "mstbin"."""
+    from .graph import _NODE_RE
+    found = []
+    for name in sorted(os.listdir(root)):
+        p = os.path.join(root, name)
+        if os.path.isdir(p):
+            files = os.listdir(p)
+            if "graph_metadata.json" in files or any(_NODE_RE.match(f) for f in files):
+                found.append((name, "dir", p))
+        elif name.endswith(".mstbin"):
+            found.append((name, "mstbin", p))
+    return found
+
+
+def batch_output_path(kind, path):
+    """Where a batch graph's ghs_mst.json goes: next to its input."""
+    if kind == "dir":
+        return os.path.join(path, "ghs_mst.json")
+    return path[: -len(".mstbin")] + ".ghs_mst.json"
+
+
+def run_batch_dir(args):
+    """--batch-dir ROOT: every graph under ROOT solved in one batch (the reference main()'s
+    six-experiment loop, ghs_implementation.py:779-833, as one call); writes each graph's ghs_mst.json
+    and ROOT/ghs_experiments.json (a list of verify.experiment_record entries)."""
+    import json
+
+    from . import graph as G
+    from .mst import minimum_spanning_forest_batch
+    from .verify import experiment_record
+    t0 = time.perf_counter()
+    items = discover_batch(args.batch_dir)
+    if not items:
+        raise FileNotFoundError(f"no graph directories or .mstbin files in {args.batch_dir}")
+    graphs = [G.read_graph_dir(p) if kind == "dir" else G.read_mstbin(p) for _, kind, p in items]
+    t_read = time.perf_counter() - t0
+    results = minimum_spanning_forest_batch(graphs)
+    records = []
+    for (name, kind, p), g, r in zip(items, graphs, results):
+        triples = r.triples()
+        G.write_result(batch_output_path(kind, p), triples)
+        records.append(experiment_record(name, g, triples))
+    exp = os.path.join(args.batch_dir, "ghs_experiments.json")
+    with open(exp, "w") as f:
+        json.dump(records, f, indent=2)
+    bad = [r["experiment"] for r in records if not r["is_correct"]]
+    if not args.quiet:
+        print("=" * 70)
+        print("Boruvka MST on MI355X (HIP) — batched solve")
+        print("=" * 70)
+        print(f"Graphs: {len(graphs)}  Edges: {sum(g.m for g in graphs)}  "
+              f"engine time: {results[0].ms_total:.3f} ms  read: {t_read * 1e3:.1f} ms")
+        for rec in records:
+            print(f"  {rec['experiment']}: n={rec['num_nodes']} m={rec['num_edges']} MST edges={rec['edges_found']} "
+                  f"weight={rec['mst_weight']} {'CORRECT' if rec['is_correct'] else 'INCORRECT'}")
+        print(f"Results saved to: {exp}")
+    return 1 if (args.check and bad) else 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="MI355X Boruvka MST (drop-in for ghs_implementation_mpi.py)")
+    ap.add_argument("--batch-dir", type=str, default=None,
+                    help="solve every graph under this directory (subdirectories, *.mstbin) in one batch")
     ap.add_argument("--graph-dir", type=str, default="graph_data", help="Graph data directory (default: graph_data)")
     ap.add_argument("--graph", type=str, default=None, help=".mstbin graph file")
     ap.add_argument("--output", type=str, default=None)
@@ -42,6 +112,8 @@ def main(argv=None):
     ap.add_argument("--scale", type=int, default=16, help="R-MAT scale (2^scale vertices) / grid side k")
     ap.add_argument("--seed", type=int, default=1, help="generator seed (weights: seed + 1)")
     args = ap.parse_args(argv)
+    if args.batch_dir is not None:
+        return run_batch_dir(args)
 
     from . import graph as G
 

@@ -48,6 +48,7 @@ EXPORTED_SYMBOLS = (
     "ghs_comm_unique_id", "ghs_comm_init", "ghs_comm_destroy", "ghs_solver_run", "ghs_mst_emulated",
     "ghs_release_cache", "ghs_slot_retries", "ghs_flags_to_eids",
     "ghs_mst_device_csr", "ghs_csr_offsets", "ghs_solver_create_csr",
+    "ghs_batch_workspace_bytes", "ghs_mst_batch_device", "ghs_mst_batch_host",
 )
 
 
@@ -124,6 +125,27 @@ class Result(ctypes.Structure):
         ("reused", ctypes.c_uint32),
         ("reserved", ctypes.c_uint32),
     ]
+
+
+class BatchResult(ctypes.Structure):
+    """ghs_batch_result_t: one graph of a batched solve (ghs_mst_batch_device / ghs_mst_batch_host)."""
+    _fields_ = [
+        ("total_weight", ctypes.c_uint64),
+        ("num_mst_edges", ctypes.c_uint32),
+        ("rounds", ctypes.c_uint32),
+        ("status", ctypes.c_uint32),  # 0 ok, 1 not canonical, 2 round cap, 3 over the size caps
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
+# the same layout as a numpy structured dtype (a device buffer of results viewed on the host)
+BATCH_RESULT_DTYPE = [("total_weight", "<u8"), ("num_mst_edges", "<u4"), ("rounds", "<u4"), ("status", "<u4"),
+                      ("reserved", "<u4")]
+BATCH_MAX_VERTICES = 4096   # GHS_BATCH_MAX_VERTICES
+BATCH_MAX_EDGES = 1 << 20   # GHS_BATCH_MAX_EDGES
+# largest vertex count of each size class of the batch kernel (csrc/batch.hip CLS_N): a graph runs in
+# the first class it fits, on 64 / 256 / 1024 threads with 12 B of LDS per class vertex
+BATCH_CLASS_LIMITS = (64, 512, 4096)
 
 
 class KernelRecord(ctypes.Structure):
@@ -293,6 +315,10 @@ def load():
             "ghs_mst_device_csr": (i32, [u32, u64, vp, vp, vp, vp, P(Config), vp, sz, vp, vp, P(Result), P(RoundStats)]),
             "ghs_csr_offsets": (i32, [u32, u64, vp, vp, vp]),
             "ghs_solver_create_csr": (i32, [u32, u64, vp, vp, vp, vp, u64, u64, P(Config), vp, sz, vp, vp, P(vp)]),
+            # ABI 10 addition: the batched solve
+            "ghs_batch_workspace_bytes": (sz, [u32]),
+            "ghs_mst_batch_device": (i32, [u32, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp]),
+            "ghs_mst_batch_host": (i32, [u32, vp, vp, vp, vp, vp, vp, vp]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(L, name)

@@ -186,6 +186,68 @@ class DeviceMST:
         return self.in_mst[: self.edges.m].cpu().numpy().astype(bool)
 
 
+class DeviceBatch:
+    """Many small graphs in batch-canonical form as torch tensors (int32 holding uint32 bit
+    patterns): nvert[B], eoff[B + 1], u / v / w of eoff[B] entries, vertex ids local to each graph,
+    graph g's canonical slice at [eoff[g], eoff[g + 1]) (include/ghs_mst.h, "batched solve")."""
+
+    def __init__(self, nvert, eoff, u, v, w):
+        self.nvert, self.eoff, self.u, self.v, self.w = nvert, eoff, u, v, w
+
+    @property
+    def num_graphs(self):
+        return int(self.nvert.numel())
+
+    @property
+    def m(self):
+        return int(self.u.numel())
+
+    @property
+    def device(self):
+        return self.nvert.device
+
+    @classmethod
+    def from_graphs(cls, graphs, device="cuda"):
+        """[CanonicalGraph] -> one packed batch (H2D copy). Graphs over the batch caps are packed as
+        they are: batch_mst reports them with status 3."""
+        from .mst import pack_batch
+
+        def dev(a):
+            return torch.from_numpy(a.view("int32").copy()).to(device)
+        return cls(*(dev(a) for a in pack_batch(list(graphs))))
+
+    def to_host(self):
+        """The batch as a list of CanonicalGraph (D2H copy)."""
+        from .graph import CanonicalGraph
+        nvert = self.nvert.cpu().numpy().view("uint32")
+        eoff = self.eoff.cpu().numpy().view("uint32").tolist()
+        u, v, w = (t.cpu().numpy().view("uint32") for t in (self.u, self.v, self.w))
+        return [CanonicalGraph(int(nvert[g]), u[eoff[g]:eoff[g + 1]], v[eoff[g]:eoff[g + 1]], w[eoff[g]:eoff[g + 1]])
+                for g in range(len(nvert))]
+
+
+def batch_mst(batch):
+    """Solve every graph of a DeviceBatch in one launch on torch's current stream
+    (ghs_mst_batch_device: one workgroup per graph, no host sync while enqueueing). Returns
+    (in_mst uint8 device tensor of batch.m flags, results): results is a structured numpy array
+    (_native.BATCH_RESULT_DTYPE, one entry per graph) read after the stream's sync; per-graph
+    problems are reported only in results["status"]."""
+    import numpy as np
+    L = _native.load()
+    _native.require_gpu()
+    B, dev = batch.num_graphs, batch.device
+    in_mst = torch.empty(max(batch.m, 1), dtype=torch.uint8, device=dev)
+    if B == 0:
+        return in_mst[:0], np.zeros(0, dtype=_native.BATCH_RESULT_DTYPE)
+    ws_bytes = int(L.ghs_batch_workspace_bytes(B))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    res = torch.empty(B * ctypes.sizeof(_native.BatchResult), dtype=torch.uint8, device=dev)
+    _native.check(L.ghs_mst_batch_device(B, _ptr(batch.nvert), _ptr(batch.eoff), _ptr(batch.u), _ptr(batch.v),
+                                         _ptr(batch.w), _ptr(ws), ws_bytes, _ptr(in_mst), _ptr(res), _stream()))
+    torch.cuda.current_stream().synchronize()
+    return in_mst[: batch.m], res.cpu().numpy().view(_native.BATCH_RESULT_DTYPE)
+
+
 def flags_to_eids(in_mst, lo, hi, capacity=None):
     """The edge ids e in [lo, hi) with in_mst[e] != 0, ascending, as an int64 device tensor — on the
     device (ghs_flags_to_eids: a flagged select), never through torch.nonzero (whose first call per

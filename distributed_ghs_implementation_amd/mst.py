@@ -83,6 +83,75 @@ def minimum_spanning_forest(graph, num_gpus=1, devices=None, config=None):
     return out
 
 
+def fits_batch(graph):
+    """True when the batch kernel takes the graph (GHS_BATCH_MAX_VERTICES / GHS_BATCH_MAX_EDGES)."""
+    return graph.n <= _native.BATCH_MAX_VERTICES and graph.m <= _native.BATCH_MAX_EDGES
+
+
+def pack_batch(graphs):
+    """CanonicalGraphs -> the batch-canonical arrays (nvert[B], eoff[B + 1], u, v, w: uint32, vertex
+    ids local to each graph, graph g's edges at [eoff[g], eoff[g + 1]))."""
+    nvert = np.array([g.n for g in graphs], dtype=np.uint32)
+    eoff = np.zeros(len(graphs) + 1, dtype=np.int64)
+    np.cumsum([g.m for g in graphs], out=eoff[1:])
+    if int(eoff[-1]) >= (1 << 31):
+        raise ValueError("a batch holds fewer than 2^31 edges")
+
+    def cat(name):
+        parts = [getattr(g, name) for g in graphs if g.m]
+        return np.concatenate(parts).astype(np.uint32, copy=False) if parts else np.zeros(0, np.uint32)
+    return nvert, eoff.astype(np.uint32), cat("u"), cat("v"), cat("w")
+
+
+def split_batch(graphs):
+    """Indices of the graphs the batch kernel takes, and of those over its caps (order kept)."""
+    small = [i for i, g in enumerate(graphs) if fits_batch(g)]
+    large = [i for i, g in enumerate(graphs) if not fits_batch(g)]
+    return small, large
+
+
+def minimum_spanning_forest_batch(graphs):
+    """Many small graphs in one launch: [CanonicalGraph] -> [MSTResult] in the same order
+    (ghs_mst_batch_host: one workgroup per graph, the whole solve in LDS — the reference's experiment
+    loop, ghs_implementation.py main(), as one call). A graph over the batch caps goes through
+    minimum_spanning_forest. A batched result has stats = [] and ms_total = the whole batch call's
+    time; rank-mapped weights report the caller's values, as the single solve does."""
+    graphs = list(graphs)
+    for g in graphs:
+        if not isinstance(g, CanonicalGraph):
+            raise TypeError("expected CanonicalGraphs (use graph.canonicalize)")
+    if not graphs:
+        return []
+    L = _native.load()
+    _native.require_gpu()
+    small, large = split_batch(graphs)
+    out = [None] * len(graphs)
+    if small:
+        sub = [graphs[i] for i in small]
+        nvert, eoff, u, v, w = pack_batch(sub)
+        M = int(eoff[-1])
+        in_mst = np.zeros(max(M, 1), dtype=np.uint8)
+        res = (_native.BatchResult * len(sub))()
+        t0 = time.perf_counter()
+        _native.check(L.ghs_mst_batch_host(len(sub), nvert.ctypes.data, eoff.ctypes.data, u.ctypes.data, v.ctypes.data,
+                                           w.ctypes.data, in_mst.ctypes.data, res))
+        ms = (time.perf_counter() - t0) * 1e3
+        rs = np.frombuffer(res, dtype=_native.BATCH_RESULT_DTYPE)
+        cs = np.concatenate([[0], np.cumsum(in_mst[:M], dtype=np.int64)])
+        cnt = (cs[eoff[1:]] - cs[eoff[:-1]]).tolist()
+        dev_cnt = rs["num_mst_edges"].tolist()
+        eo = eoff.tolist()
+        for k, i in enumerate(small):
+            g = graphs[i]
+            flags = in_mst[eo[k]:eo[k + 1]]
+            if cnt[k] != dev_cnt[k]:
+                raise _native.GHSError(_native.GHS_E_STATE, f"batch graph {i}: in_mst count disagrees with the device edge counter")
+            out[i] = MSTResult(g, flags, int(rs["total_weight"][k]), int(rs["rounds"][k]), [], ms)
+    for i in large:
+        out[i] = minimum_spanning_forest(graphs[i])
+    return out
+
+
 class _WeightView:
     """Minimal `graph[u][v]["weight"]` view (the reference harness reads weights this way)."""
 

@@ -227,6 +227,43 @@ int ghs_mst_device_csr(uint32_t n, uint64_t m, const uint32_t *d_off, const uint
 /* d_off (n + 1 uint32) from a canonical COO list's d_u (u ascending), on the device */
 int ghs_csr_offsets(uint32_t n, uint64_t m, const uint32_t *d_u, uint32_t *d_off, void *stream);
 
+/* ---- batched solve: many small graphs in one launch (ABI 10 addition) ----------------------
+ * Replaces the reference's experiment loop (ghs_implementation.py main(): six Erdos-Renyi graphs
+ * of a few dozen vertices solved one after another into ghs_experiments.json) as ONE call: B graphs
+ * concatenated in "batch-canonical" form — nvert[B] vertex counts, eoff[B + 1] edge offsets
+ * (eoff[0] = 0, nondecreasing, eoff[B] = M < 2^31), u / v / w of M uint32 each (16-byte aligned on
+ * the device); graph g owns the slice [eoff[g], eoff[g + 1]) with vertex ids LOCAL to the graph
+ * (u < v < nvert[g]), canonical on its own; its edge ids are e - eoff[g] and its keys
+ * (uint64)w << 32 | local eid, so every graph's flags equal canonical Kruskal's bit for bit.
+ * One workgroup solves one graph entirely in LDS (csrc/batch.hip); graphs are validated by the same
+ * kernel and a bad graph never disturbs its neighbours: per-graph problems are reported only in
+ * ghs_batch_result_t.status, and every flag byte of a slice with monotone offsets is written (0 for
+ * a graph with status 1 or 3). The two caps are design choices (one workgroup must not become the
+ * batch's long pole; past them ghs_mst_device is the right tool). */
+#define GHS_BATCH_MAX_VERTICES 4096u
+#define GHS_BATCH_MAX_EDGES (1u << 20)
+typedef struct ghs_batch_result {   /* 24 bytes, one per graph */
+  uint64_t total_weight;
+  uint32_t num_mst_edges;
+  uint32_t rounds;    /* edge scans executed */
+  uint32_t status;    /* 0 ok, 1 not canonical, 2 round cap, 3 over the size caps */
+  uint32_t reserved;
+} ghs_batch_result_t;
+size_t ghs_batch_workspace_bytes(uint32_t num_graphs);
+/* Asynchronous on `stream`: enqueues the classify + solve kernels and returns without a host sync;
+ * d_in_mst (M bytes) and d_results (num_graphs entries) are complete once the stream is
+ * synchronized. GHS_E_ARG: NULL / misaligned pointers; GHS_E_NOMEM: workspace_bytes short. */
+int ghs_mst_batch_device(uint32_t num_graphs, const uint32_t *d_nvert, const uint32_t *d_eoff,
+                         const uint32_t *d_u, const uint32_t *d_v, const uint32_t *d_w,
+                         void *d_workspace, size_t workspace_bytes, uint8_t *d_in_mst,
+                         ghs_batch_result_t *d_results, void *stream);
+/* Host arrays: copies in, runs, copies out, syncs. results and the healthy graphs' flags are filled
+ * in even when the call returns GHS_E_NONCANON / GHS_E_ROUNDCAP / GHS_E_ARG for a graph of status
+ * 1 / 2 / 3 (the first such graph's index is in ghs_last_error()). num_graphs == 0: GHS_OK. */
+int ghs_mst_batch_host(uint32_t num_graphs, const uint32_t *nvert, const uint32_t *eoff,
+                       const uint32_t *u, const uint32_t *v, const uint32_t *w,
+                       uint8_t *in_mst, ghs_batch_result_t *results);
+
 /* device-side canonicity check: *ok = 1 iff u < v < n and (u, v) strictly ascending */
 int ghs_check_canonical(uint32_t n, uint64_t m, const uint32_t *d_u, const uint32_t *d_v, void *stream, int *ok);
 
