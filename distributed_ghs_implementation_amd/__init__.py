@@ -7,14 +7,17 @@ Entry points mirroring the reference:
   python -m distributed_ghs_implementation_amd --graph-dir D
                                             ghs_implementation_mpi.py:884-954 (CLI)
 Array level: graph.canonicalize -> mst.minimum_spanning_forest (many small graphs in one launch:
-mst.minimum_spanning_forest_batch); device level: device.DeviceMST, device.batch_mst; multi-GPU:
-distributed.DistributedMST.
+mst.minimum_spanning_forest_batch; raw edge arrays canonicalized on the device:
+mst.minimum_spanning_forest_edges); device level: device.DeviceMST, device.batch_mst,
+device.canonicalize_device; multi-GPU: distributed.DistributedMST.
 """
 from .graph import (CanonicalGraph, canonicalize, read_graph_dir, read_mstbin, write_graph_dir, write_mstbin,
                     write_result)
-from .mst import GHSAlgorithm, MSTResult, minimum_spanning_forest, minimum_spanning_forest_batch
+from .mst import (GHSAlgorithm, MSTResult, minimum_spanning_forest, minimum_spanning_forest_batch,
+                  minimum_spanning_forest_edges)
 
 __all__ = [
     "CanonicalGraph", "canonicalize", "read_graph_dir", "read_mstbin", "write_graph_dir", "write_mstbin",
     "write_result", "GHSAlgorithm", "MSTResult", "minimum_spanning_forest", "minimum_spanning_forest_batch",
+    "minimum_spanning_forest_edges",
 ]

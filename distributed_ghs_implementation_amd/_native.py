@@ -49,6 +49,7 @@ EXPORTED_SYMBOLS = (
     "ghs_release_cache", "ghs_slot_retries", "ghs_flags_to_eids",
     "ghs_mst_device_csr", "ghs_csr_offsets", "ghs_solver_create_csr",
     "ghs_batch_workspace_bytes", "ghs_mst_batch_device", "ghs_mst_batch_host",
+    "ghs_canonicalize_temp_bytes", "ghs_canonicalize_device",
 )
 
 
@@ -319,6 +320,9 @@ def load():
             "ghs_batch_workspace_bytes": (sz, [u32]),
             "ghs_mst_batch_device": (i32, [u32, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp]),
             "ghs_mst_batch_host": (i32, [u32, vp, vp, vp, vp, vp, vp, vp]),
+            # ABI 10 addition: device ingest (raw edge list -> canonical list + raw indices)
+            "ghs_canonicalize_temp_bytes": (sz, [u32, u64]),
+            "ghs_canonicalize_device": (i32, [u32, u64, vp, vp, vp, vp, vp, vp, vp, P(u64), vp, sz, vp]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(L, name)

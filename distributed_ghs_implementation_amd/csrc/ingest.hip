@@ -5,7 +5,9 @@
 // graph_metadata.json). The reference's generator is networkx's seeded ER G(n, p)
 // (create_graph_files.py:13-40); R-MAT and grids are the BASELINE scales it cannot reach. The
 // canonical sort/dedupe is a rocPRIM radix sort of 64-bit (min << scale | max) keys, then a
-// two-pass unique + decode (k_uniq_*).
+// two-pass unique + decode (k_uniq_*). ghs_canonicalize_device is the general form of that stage for
+// a caller's raw edge list (k_canon_*: the nx.Graph construction every reference entry point starts
+// with, ghs_implementation.py:425-426, on the device).
 // The CPU restatement of both generators (test infrastructure) is oracle/generators.c.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -205,6 +207,151 @@ __global__ __launch_bounds__(UQ_BLOCK) void k_uniq_write(const uint64_t *__restr
   }
 }
 
+// ---- canonicalize (ABI 10 addition, ghs_canonicalize_device) ---------------------------------
+// The general form of the stage above for a caller's raw edge list: any n, the caller's weights,
+// nx.Graph "last write wins" for a repeated pair, range validation, and the raw index of the
+// surviving occurrence. Pass 1 (k_canon_keys) packs (min << bits | max) keys with the raw index as
+// the value; a self-loop and an edge with an endpoint >= n both become the marker (all ones over
+// 2 * bits bits: the pair (2^bits - 1, 2^bits - 1), itself a self-loop, so no real edge has it), the
+// latter also raising the error flag. rocPRIM's pairs sort is stable, so a run of equal keys keeps
+// ascending raw index and its LAST entry is the occurrence nx.Graph would keep: the compaction
+// (k_canon_count / k_uniq_scan / k_canon_write) keeps an entry that differs from its successor.
+typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ uint64_t canon_key(uint32_t a, uint32_t b, uint32_t n, uint32_t bits, uint64_t marker,
+                                              bool *bad) {
+  if (a >= n || b >= n) {
+    *bad = true;
+    return marker;
+  }
+  if (a == b) return marker;
+  const uint32_t lo = a < b ? a : b, hi = a < b ? b : a;
+  return ((uint64_t)lo << bits) | hi;
+}
+
+// Elements [head, head + 4 * nquads) are read as 16-byte vectors (the host picks head so that both
+// ru + head and rv + head are 16-byte aligned, or nquads = 0 when no such head exists); the other
+// nscalar elements — the first `head` and the tail past the quads — one by one. keys / vals are
+// 256-byte aligned, so with head = 0 (the aligned caller) the stores are 16-byte vectors too.
+__global__ __launch_bounds__(BLOCK) void k_canon_keys(uint32_t n, uint32_t bits, uint64_t marker, uint64_t head,
+                                                      uint64_t nquads, uint64_t nscalar,
+                                                      const uint32_t *__restrict__ ru, const uint32_t *__restrict__ rv,
+                                                      uint64_t *__restrict__ keys, uint32_t *__restrict__ vals,
+                                                      unsigned int *__restrict__ err) {
+  const uint64_t gid = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  bool bad = false;
+  for (uint64_t q = gid; q < nquads; q += stride) {
+    const uint64_t i = head + 4 * q;
+    const u32x4 a = *reinterpret_cast<const u32x4 *>(ru + i);
+    const u32x4 b = *reinterpret_cast<const u32x4 *>(rv + i);
+    const uint64_t k0 = canon_key(a.x, b.x, n, bits, marker, &bad);
+    const uint64_t k1 = canon_key(a.y, b.y, n, bits, marker, &bad);
+    const uint64_t k2 = canon_key(a.z, b.z, n, bits, marker, &bad);
+    const uint64_t k3 = canon_key(a.w, b.w, n, bits, marker, &bad);
+    const uint32_t i0 = (uint32_t)i;
+    if (head == 0) {
+      u64x2 lo, hi;
+      lo.x = k0; lo.y = k1; hi.x = k2; hi.y = k3;
+      u32x4 iv;
+      iv.x = i0; iv.y = i0 + 1; iv.z = i0 + 2; iv.w = i0 + 3;
+      *reinterpret_cast<u64x2 *>(keys + i) = lo;
+      *reinterpret_cast<u64x2 *>(keys + i + 2) = hi;
+      *reinterpret_cast<u32x4 *>(vals + i) = iv;
+    } else {
+      keys[i] = k0; keys[i + 1] = k1; keys[i + 2] = k2; keys[i + 3] = k3;
+      vals[i] = i0; vals[i + 1] = i0 + 1; vals[i + 2] = i0 + 2; vals[i + 3] = i0 + 3;
+    }
+  }
+  for (uint64_t s = gid; s < nscalar; s += stride) {
+    const uint64_t i = s < head ? s : 4 * nquads + s;
+    keys[i] = canon_key(ru[i], rv[i], n, bits, marker, &bad);
+    vals[i] = (uint32_t)i;
+  }
+  if (bad) atomicOr(err, 1u);
+}
+
+// a sorted entry survives when it is not the marker and its successor (read across lane, wave,
+// block and tile boundaries alike: it is the next array element) has another key
+__device__ __forceinline__ bool cn_keep(const uint64_t *__restrict__ keys, uint64_t i, uint64_t T, uint64_t marker,
+                                        uint64_t *k_out) {
+  if (i >= T) return false;
+  const uint64_t k = keys[i];
+  *k_out = k;
+  return k != marker && (i + 1 == T || keys[i + 1] != k);
+}
+
+__global__ __launch_bounds__(UQ_BLOCK) void k_canon_count(const uint64_t *__restrict__ keys, uint64_t T,
+                                                          uint64_t marker, uint32_t *__restrict__ tile_cnt) {
+  __shared__ uint32_t s_w[UQ_BLOCK / 64];
+  const uint64_t base = blockIdx.x * UQ_TILE;
+  uint32_t c = 0;
+#pragma unroll
+  for (int j = 0; j < UQ_ROWS; ++j) {
+    uint64_t k;
+    c += cn_keep(keys, base + (uint64_t)j * UQ_BLOCK + threadIdx.x, T, marker, &k) ? 1u : 0u;
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d);
+  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x / 64] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t t = 0;
+    for (int w = 0; w < UQ_BLOCK / 64; ++w) t += s_w[w];
+    tile_cnt[blockIdx.x] = t;
+  }
+}
+
+// each survivor, at its rank: (u, v) decoded from the key, src = its raw index (the sorted value),
+// w = rw[src] — a gather, for survivors only. src may be NULL.
+__global__ __launch_bounds__(UQ_BLOCK) void k_canon_write(const uint64_t *__restrict__ keys,
+                                                          const uint32_t *__restrict__ vals, uint64_t T,
+                                                          uint64_t marker, const uint32_t *__restrict__ tile_off,
+                                                          uint32_t bits, const uint32_t *__restrict__ rw,
+                                                          uint32_t *__restrict__ u, uint32_t *__restrict__ v,
+                                                          uint32_t *__restrict__ w, uint32_t *__restrict__ src) {
+  __shared__ uint32_t s_cnt[UQ_ROWS][UQ_BLOCK / 64];
+  const uint64_t base = blockIdx.x * UQ_TILE;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x / 64;
+  const uint64_t lt = (1ull << lane) - 1ull;
+  uint64_t kk[UQ_ROWS];
+  uint64_t masks[UQ_ROWS];
+#pragma unroll
+  for (int j = 0; j < UQ_ROWS; ++j) {
+    const bool keep = cn_keep(keys, base + (uint64_t)j * UQ_BLOCK + threadIdx.x, T, marker, &kk[j]);
+    masks[j] = __ballot(keep);
+    if (lane == 0) s_cnt[j][wid] = (uint32_t)__popcll(masks[j]);
+  }
+  __syncthreads();
+  const uint64_t vmask = (1ull << bits) - 1ull;  // bits <= 32
+  uint32_t row_base = tile_off[blockIdx.x];
+#pragma unroll
+  for (int j = 0; j < UQ_ROWS; ++j) {
+    uint32_t before = 0, row = 0;
+#pragma unroll
+    for (int x = 0; x < UQ_BLOCK / 64; ++x) {
+      const uint32_t c = s_cnt[j][x];
+      before += x < wid ? c : 0u;
+      row += c;
+    }
+    if ((masks[j] >> lane) & 1ull) {
+      const uint32_t o = row_base + before + (uint32_t)__popcll(masks[j] & lt);
+      const uint32_t r = vals[base + (uint64_t)j * UQ_BLOCK + threadIdx.x];
+      u[o] = (uint32_t)(kk[j] >> bits);
+      v[o] = (uint32_t)(kk[j] & vmask);
+      w[o] = rw[r];
+      if (src) src[o] = r;
+    }
+    row_base += row;
+  }
+}
+
+static inline uint32_t canon_bits(uint32_t n) {
+  uint32_t bits = 1;
+  while (bits < 32 && (1ull << bits) < n) ++bits;
+  return bits;
+}
+
 // ---- grid ----------------------------------------------------------------------------------
 __global__ void k_grid(uint32_t k, uint32_t mode, uint64_t wseed, uint32_t *__restrict__ u, uint32_t *__restrict__ v,
                        uint32_t *__restrict__ w) {
@@ -296,6 +443,84 @@ int ghs_rmat_generate(uint32_t scale, uint32_t edgefactor, uint64_t seed, uint64
   GHS_HIP_CHECK(hipMemcpyAsync(&cnt, nsel, 8, hipMemcpyDeviceToHost, st));
   GHS_HIP_CHECK(hipStreamSynchronize(st));
   *m_out = cnt;
+  return GHS_OK;
+}
+
+// temp layout: keys in / out (8 B per raw edge each), raw indices in / out (4 B each), a 256-byte
+// status block (canonical count, error flag), then rocPRIM's sort storage, reused for the tile counts
+static size_t canon_prim_bytes(uint32_t n, uint64_t m_raw) {
+  size_t sort_b = 0;
+  (void)rocprim::radix_sort_pairs(nullptr, sort_b, (const uint64_t *)nullptr, (uint64_t *)nullptr,
+                                  (const uint32_t *)nullptr, (uint32_t *)nullptr, (size_t)m_raw, 0u,
+                                  2u * canon_bits(n));
+  const size_t tiles_b = ((m_raw + UQ_TILE - 1) / UQ_TILE) * 4;
+  return align256(sort_b > tiles_b ? sort_b : tiles_b);
+}
+
+size_t ghs_canonicalize_temp_bytes(uint32_t n, uint64_t m_raw) {
+  if (m_raw == 0 || m_raw >= (1ull << 32)) return 0;
+  return 2 * align256(m_raw * 8) + 2 * align256(m_raw * 4) + 256 + canon_prim_bytes(n, m_raw);
+}
+
+int ghs_canonicalize_device(uint32_t n, uint64_t m_raw, const uint32_t *d_ru, const uint32_t *d_rv,
+                            const uint32_t *d_rw, uint32_t *d_u, uint32_t *d_v, uint32_t *d_w, uint32_t *d_src,
+                            uint64_t *m_out, void *d_temp, size_t temp_bytes, void *stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!m_out) GHS_FAIL(GHS_E_ARG, "m_out is NULL");
+  *m_out = 0;
+  if (m_raw == 0) return GHS_OK;
+  if (m_raw >= (1ull << 32)) GHS_FAIL(GHS_E_ARG, "m_raw must be < 2^32");
+  if (!d_ru || !d_rv || !d_rw || !d_u || !d_v || !d_w || !d_temp) GHS_FAIL(GHS_E_ARG, "NULL pointer");
+  if (((uintptr_t)d_ru | (uintptr_t)d_rv | (uintptr_t)d_rw) & 3)
+    GHS_FAIL(GHS_E_ARG, "raw u, v, w must be 4-byte aligned");
+  if (((uintptr_t)d_u | (uintptr_t)d_v | (uintptr_t)d_w | (uintptr_t)d_src | (uintptr_t)d_temp) & 15)
+    GHS_FAIL(GHS_E_ARG, "outputs and temp must be 16-byte aligned");
+  if (temp_bytes < ghs_canonicalize_temp_bytes(n, m_raw)) GHS_FAIL(GHS_E_NOMEM, "temp too small");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) GHS_FAIL(GHS_E_NODEVICE, "no HIP device");
+
+  const uint64_t T = m_raw;
+  const size_t a8 = align256(T * 8), a4 = align256(T * 4);
+  char *base = (char *)d_temp;
+  uint64_t *ka = (uint64_t *)base;
+  uint64_t *kb = (uint64_t *)(base + a8);
+  uint32_t *va = (uint32_t *)(base + 2 * a8);
+  uint32_t *vb = (uint32_t *)(base + 2 * a8 + a4);
+  uint64_t *status = (uint64_t *)(base + 2 * a8 + 2 * a4);  // [0] canonical count, [1] error flag
+  void *prim_temp = base + 2 * a8 + 2 * a4 + 256;
+  size_t prim_bytes = canon_prim_bytes(n, T);
+  const uint64_t ntiles = (T + UQ_TILE - 1) / UQ_TILE;
+  uint32_t *tiles = (uint32_t *)prim_temp;  // reused after the sort
+  const uint32_t bits = canon_bits(n);
+  const uint64_t marker = bits >= 32 ? ~0ull : ((1ull << (2 * bits)) - 1ull);
+
+  // the 16-byte vector body of pass 1: from the first element at which ru is 16-byte aligned, when
+  // rv is aligned there too (slices of separate allocations usually are; else all scalar)
+  uint64_t head = ((16 - ((uintptr_t)d_ru & 15)) & 15) / 4, nquads = 0, nscalar = T;
+  if (head > T) head = T;
+  if ((((uintptr_t)d_rv + 4 * head) & 15) == 0) {
+    nquads = (T - head) / 4;
+    nscalar = T - 4 * nquads;
+  } else {
+    head = 0;
+  }
+
+  GHS_HIP_CHECK(hipMemsetAsync(status, 0, 16, st));
+  k_canon_keys<<<grid_cap(nquads > nscalar ? nquads : nscalar, BLOCK, 2048), BLOCK, 0, st>>>(
+      n, bits, marker, head, nquads, nscalar, d_ru, d_rv, ka, va, (unsigned int *)(status + 1));
+  GHS_HIP_CHECK(hipGetLastError());
+  GHS_HIP_CHECK(rocprim::radix_sort_pairs(prim_temp, prim_bytes, ka, kb, va, vb, (size_t)T, 0u, 2u * bits, st));
+  k_canon_count<<<(unsigned)ntiles, UQ_BLOCK, 0, st>>>(kb, T, marker, tiles);
+  k_uniq_scan<<<1, 1024, 0, st>>>(tiles, (uint32_t)ntiles, status);
+  k_canon_write<<<(unsigned)ntiles, UQ_BLOCK, 0, st>>>(kb, vb, T, marker, tiles, bits, d_rw, d_u, d_v, d_w, d_src);
+  GHS_HIP_CHECK(hipGetLastError());
+  uint64_t h_status[2] = {0, 0};
+  GHS_HIP_CHECK(hipMemcpyAsync(h_status, status, 16, hipMemcpyDeviceToHost, st));
+  GHS_HIP_CHECK(hipStreamSynchronize(st));
+  if (h_status[1])
+    GHS_FAIL(GHS_E_ARG, "vertex id out of range: a raw endpoint is >= n = " + std::to_string(n));
+  if (h_status[0] >= (1ull << 31)) GHS_FAIL(GHS_E_ARG, "the canonical edge count must be < 2^31");
+  *m_out = h_status[0];
   return GHS_OK;
 }
 

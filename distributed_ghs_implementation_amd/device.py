@@ -28,12 +28,14 @@ class DeviceEdges:
     """Canonical edge list in HBM: n, u/v/w as int32 tensors holding uint32 bit patterns. `off`
     (ABI 9, optional): the CSR row offsets of the same list (n + 1 entries, `with_csr()`); an
     engine built with csr=True streams (off, v, w) — 8 B per edge instead of 12 — and u may then
-    be dropped (`csr_only()`)."""
+    be dropped (`csr_only()`). `src` (optional, lists made by `canonicalize_device` / `from_raw`):
+    per canonical edge, the index of the caller's raw edge it came from (int32, uint32 bits)."""
 
-    def __init__(self, n, u, v, w, off=None):
+    def __init__(self, n, u, v, w, off=None, src=None):
         self.n = int(n)
         self.u, self.v, self.w = u, v, w
         self.off = off
+        self.src = src
 
     @property
     def m(self):
@@ -51,7 +53,7 @@ class DeviceEdges:
     def csr_only(self):
         """The CSR form alone (u released): off, v, w."""
         self.with_csr()
-        return DeviceEdges(self.n, None, self.v, self.w, self.off)
+        return DeviceEdges(self.n, None, self.v, self.w, self.off, self.src)
 
     @property
     def device(self):
@@ -63,6 +65,25 @@ class DeviceEdges:
         def dev(a):
             return torch.from_numpy(a.view("int32").copy()).to(device)
         return cls(graph.n, dev(graph.u), dev(graph.v), dev(graph.w))
+
+    @classmethod
+    def from_raw(cls, n, u, v, w, device="cuda"):
+        """Raw numpy integer arrays (any order, either orientation, repeats, self-loops) -> the
+        canonical list, sorted and de-duplicated on the device (`canonicalize_device`): one H2D copy
+        of the three arrays, no host sort. Values outside [0, 2^32) raise ValueError."""
+        packed = _pack_raw(u, v, w)
+        _native.load()
+        _native.require_gpu()
+        dev = torch.from_numpy(packed.view("int32")).to(device)
+        return canonicalize_device(n, dev[0], dev[1], dev[2])
+
+    def raw_eids(self, in_mst):
+        """The caller's edge indices of the MSF edges (in_mst: the m flags of a solve of this list),
+        in canonical order, as an int64 device tensor."""
+        if self.src is None:
+            raise ValueError("this edge list carries no raw indices (build it with canonicalize_device / from_raw)")
+        eids = flags_to_eids(in_mst, 0, self.m)
+        return self.src[eids].to(torch.int64) & 0xFFFFFFFF
 
     def u_host(self):
         """u as a host uint32 array (expanded from the offsets for a CSR-only list)."""
@@ -76,6 +97,80 @@ class DeviceEdges:
         from .graph import CanonicalGraph
         return CanonicalGraph(self.n, self.u_host(), self.v.cpu().numpy().view("uint32"),
                               self.w.cpu().numpy().view("uint32"))
+
+
+def _pack_raw(u, v, w):
+    """Raw numpy integer arrays -> one (3, m) uint32 array (a single H2D copy); ValueError for
+    anything but integers in [0, 2^32)."""
+    import numpy as np
+    arrs = [np.asarray(a) for a in (u, v, w)]
+    m = len(arrs[0]) if arrs[0].ndim == 1 else -1
+    if any(a.ndim != 1 or len(a) != m for a in arrs):
+        raise ValueError("u, v, w must be one-dimensional arrays of equal length")
+    packed = np.empty((3, m), dtype=np.uint32)
+    for k, (name, a) in enumerate(zip(("u", "v", "w"), arrs)):
+        if a.size == 0:
+            continue
+        if a.dtype.kind not in "iu":
+            raise ValueError(f"{name}: the device ingest takes integers in [0, 2^32) only "
+                             "(graph.canonicalize accepts any numeric weights)")
+        if int(a.min()) < 0 or int(a.max()) >= (1 << 32):
+            raise ValueError(f"{name}: values must be in [0, 2^32) "
+                             "(graph.canonicalize accepts any numeric weights)")
+        packed[k] = a.astype(np.uint32, copy=False)
+    return packed
+
+
+def _as_u32_tensor(t, name):
+    """A device tensor of uint32 bit patterns: int32 as it is, int64 range-checked on the device
+    (one flag read back) and narrowed."""
+    if t.dtype == torch.int32:
+        return t.contiguous()
+    if t.dtype != torch.int64:
+        raise ValueError(f"{name}: int32 (uint32 bit patterns) or int64 tensor expected, got {t.dtype}")
+    if t.numel() and bool(((t < 0) | (t >= (1 << 32))).any()):
+        raise ValueError(f"{name}: values must be in [0, 2^32)")
+    return torch.where(t >= (1 << 31), t - (1 << 32), t).to(torch.int32)
+
+
+def canonicalize_device(n, u, v, w, keep_src=True):
+    """Raw edges in HBM -> canonical DeviceEdges, without leaving the device
+    (ghs_canonicalize_device: key pass, stable pairs sort, last-of-run compaction). u, v, w: torch
+    tensors on the GPU, int32 (uint32 bit patterns) or int64 (range-checked, ValueError outside
+    [0, 2^32)); any vertex order, either orientation, repeats and self-loops allowed, with
+    nx.Graph semantics (self-loops dropped, the LAST weight given for a pair wins). keep_src: the
+    result's `src` holds, per canonical edge, the index of the raw edge it came from (`raw_eids`).
+    Runs on torch's current stream; a vertex id >= n raises GHSError (GHS_E_ARG)."""
+    n = int(n)
+    if n < 0 or n >= (1 << 32):
+        raise ValueError("n must be in [0, 2^32)")
+    L = _native.load()
+    _native.require_gpu()
+    for name, t in (("u", u), ("v", v), ("w", w)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 1):
+            raise ValueError(f"{name}: a one-dimensional GPU tensor expected (DeviceEdges.from_raw takes numpy arrays)")
+    if not (u.numel() == v.numel() == w.numel()):
+        raise ValueError("u, v, w must have equal length")
+    if not (u.device == v.device == w.device):
+        raise ValueError("u, v, w must be on one device")
+    ru, rv, rw = _as_u32_tensor(u, "u"), _as_u32_tensor(v, "v"), _as_u32_tensor(w, "w")
+    m_raw, dev = int(ru.numel()), ru.device
+    if m_raw >= (1 << 32):
+        raise ValueError("at most 2^32 - 1 raw edges")
+    with torch.cuda.device(dev):
+        cu = torch.empty(m_raw, dtype=torch.int32, device=dev)
+        cv = torch.empty(m_raw, dtype=torch.int32, device=dev)
+        cw = torch.empty(m_raw, dtype=torch.int32, device=dev)
+        src = torch.empty(m_raw, dtype=torch.int32, device=dev) if keep_src else None
+        tb = int(L.ghs_canonicalize_temp_bytes(n, m_raw))
+        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=dev)
+        m = ctypes.c_uint64(0)
+        _native.check(L.ghs_canonicalize_device(n, m_raw, _ptr(ru), _ptr(rv), _ptr(rw), _ptr(cu), _ptr(cv), _ptr(cw),
+                                                _ptr(src), ctypes.byref(m), _ptr(tmp), tb, _stream()))
+    del tmp
+    mm = m.value
+    # views of the first m entries, as generate_rmat returns them
+    return DeviceEdges(n, cu[:mm], cv[:mm], cw[:mm], src=src[:mm] if keep_src else None)
 
 
 def generate_rmat(scale, edgefactor=16, seed=1, wseed=2, device="cuda"):

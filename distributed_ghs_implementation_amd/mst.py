@@ -29,9 +29,12 @@ from .graph import CanonicalGraph, canonicalize, mst_result_dict
 class MSTResult:
     """Spanning forest of a CanonicalGraph: in_mst mask over canonical edge ids + totals."""
 
-    def __init__(self, graph, in_mst, total_weight, rounds, stats, ms_total):
+    def __init__(self, graph, in_mst, total_weight, rounds, stats, ms_total, raw_ids=None):
         self.graph = graph
         self.in_mst = in_mst.astype(bool)
+        # minimum_spanning_forest_edges only: the caller's raw edge index of every MSF edge (int64,
+        # canonical order); None on every other path
+        self.raw_ids = raw_ids
         # the engine sums uint32 weights; for rank-mapped weights (graph.weights) the caller's
         # own values are summed over the same edges
         self.total_weight = int(total_weight) if graph.weights is None else graph.total_weight(self.in_mst)
@@ -79,6 +82,29 @@ def minimum_spanning_forest(graph, num_gpus=1, devices=None, config=None):
     st = [stats[i].as_dict() for i in range(res.num_stats)]
     out = MSTResult(graph, in_mst[:m], res.total_weight, res.rounds, st, res.ms_total)
     if out.num_edges != res.num_mst_edges:
+        raise _native.GHSError(_native.GHS_E_STATE, "in_mst count disagrees with the device edge counter")
+    return out
+
+
+def minimum_spanning_forest_edges(num_nodes, u, v, w):
+    """Raw edge arrays -> MSTResult, canonicalized on the device: u, v, w are integer arrays in any
+    order, either orientation, with repeats and self-loops (nx.Graph semantics: the last weight
+    given for a pair wins), weights in [0, 2^32). One H2D copy, the sort / de-duplication and the
+    solve on the GPU (DeviceEdges.from_raw -> DeviceMST.run), then the canonical list comes back for
+    edges() / triples() / to_dict(). `raw_ids` of the result: for every MSF edge, the index of the
+    caller's edge it is. Other weights (negative, float, larger) raise ValueError: `canonicalize`
+    rank-maps them on the host."""
+    from .device import DeviceEdges, DeviceMST
+    n = int(num_nodes)
+    if n < 0 or n >= (1 << 32):
+        raise ValueError("num_nodes must be in [0, 2^32)")
+    edges = DeviceEdges.from_raw(n, u, v, w)  # ValueError (bad values) before anything touches the device
+    eng = DeviceMST(edges)
+    res, stats = eng.run()
+    graph = edges.to_host()
+    raw_ids = edges.raw_eids(eng.in_mst).cpu().numpy().astype(np.int64)
+    out = MSTResult(graph, eng.in_mst_host(), res.total_weight, res.rounds, list(stats), res.ms_total, raw_ids=raw_ids)
+    if out.num_edges != res.num_mst_edges or len(raw_ids) != out.num_edges:
         raise _native.GHSError(_native.GHS_E_STATE, "in_mst count disagrees with the device edge counter")
     return out
 

@@ -264,6 +264,37 @@ int ghs_mst_batch_host(uint32_t num_graphs, const uint32_t *nvert, const uint32_
                        const uint32_t *u, const uint32_t *v, const uint32_t *w,
                        uint8_t *in_mst, ghs_batch_result_t *results);
 
+/* ---- device ingest: raw edge list -> canonical edge list (ABI 10 addition) ------------------
+ * Replaces the graph construction every reference entry point starts with (nx.Graph.add_edge over
+ * the caller's triples, ghs_implementation.py:425-426, check_mst.py:6-7) for edges that are already
+ * in HBM: m_raw raw edges (d_ru, d_rv, d_rw: uint32 each, any vertex ids, either orientation, repeats
+ * and self-loops allowed) become the canonical list the solver entry points take, without leaving the
+ * device. Semantics are nx.Graph's: self-loops are dropped; each unordered pair appears once as
+ * (min, max) with the weight of its LAST raw occurrence (in raw index order, whichever orientation
+ * that occurrence had); the output is ascending by (u, v). d_src (may be NULL) receives the raw index
+ * of that last occurrence per canonical edge, so min(ru[src[e]], rv[src[e]]) == u[e],
+ * max(...) == v[e], rw[src[e]] == w[e]: the map from the solver's edge ids back to the caller's.
+ * Sizes: d_u, d_v, d_w (and d_src) must have room for m_raw entries; *m_out (host) = the canonical
+ * count. Outputs and d_temp must be 16-byte aligned (what the solver requires of its inputs); the raw
+ * inputs only 4-byte (slices are fine). Outputs and d_temp must not overlap the inputs or each other:
+ * the inputs are read after the outputs are first written.
+ * d_temp: ghs_canonicalize_temp_bytes(n, m_raw) bytes (24 B per raw edge + the sort's storage, about 36 B per
+ * raw edge in all; computed on the host, no GPU needed; 0 for m_raw = 0).
+ * Pipeline: a key pass (min << bits | max with bits = max(1, ceil(log2 n)), value = raw index), a
+ * stable rocPRIM pairs sort over the 2 * bits key bits, a last-of-run compaction. Everything is
+ * enqueued on `stream`; the call returns after ONE stream synchronise that brings back the count and
+ * the error flag together.
+ * Errors, checked before any device work (so GHS_E_ARG, not GHS_E_NODEVICE, on a host without GPU):
+ * NULL / misaligned pointers, m_raw >= 2^32: GHS_E_ARG; temp_bytes short: GHS_E_NOMEM. m_raw == 0:
+ * GHS_OK, *m_out = 0, no device work, pointers may be NULL. After the sync: any raw endpoint >= n:
+ * GHS_E_ARG ("vertex id out of range"; the outputs are then unspecified, nothing was read or written
+ * out of bounds); a canonical count >= 2^31 (over the solver's cap): GHS_E_ARG. */
+size_t ghs_canonicalize_temp_bytes(uint32_t n, uint64_t m_raw);
+int ghs_canonicalize_device(uint32_t n, uint64_t m_raw,
+                            const uint32_t *d_ru, const uint32_t *d_rv, const uint32_t *d_rw,
+                            uint32_t *d_u, uint32_t *d_v, uint32_t *d_w, uint32_t *d_src /* may be NULL */,
+                            uint64_t *m_out, void *d_temp, size_t temp_bytes, void *stream);
+
 /* device-side canonicity check: *ok = 1 iff u < v < n and (u, v) strictly ascending */
 int ghs_check_canonical(uint32_t n, uint64_t m, const uint32_t *d_u, const uint32_t *d_v, void *stream, int *ok);
 
