@@ -47,6 +47,10 @@
 // labels of the fragments active at the start of round r-1, and lab[x] for exactly those labels
 // is refreshed every round by k_jump. A vertex's fragment is found by following lab[] to a
 // fixpoint (find_lab); k_resolve compresses every vertex to its root between levels.
+//
+// Parts. This file is one translation unit; a stage may live in boruvka/<part>.h, included exactly
+// once at the place its contents have in the definition order (the Makefile rebuilds boruvka.o
+// when a part changes). So far: the LDS tail (boruvka/tail.h: kernels, boruvka/tail_driver.h: host).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -80,10 +84,7 @@ constexpr int FIND_LAB_MAX_HOPS = 256;
 // per-fragment gathers of the canonical endpoints dominate; fragment form (k_hook) otherwise.
 // Chosen on the device from the exact counts; the host enqueues both only while its bound on the
 // active fragments is at least EDGE_HOOK_MIN_BOUND.
-#ifndef GHS_EDGE_HOOK_RATIO
-#define GHS_EDGE_HOOK_RATIO 4
-#endif
-constexpr uint64_t EDGE_HOOK_RATIO = GHS_EDGE_HOOK_RATIO;
+constexpr uint64_t EDGE_HOOK_RATIO = 4;  // 1 / 0 measured slower (DESIGN.md "Measured and rejected")
 constexpr uint32_t HOOK_G = 2048;  // grid cap of the kernels ending in per-block total atomics
 constexpr uint64_t EDGE_HOOK_MIN_BOUND = 1u << 20;
 constexpr uint32_t JUMP_MAX_STEPS = 1u << 26;
@@ -104,20 +105,7 @@ __device__ __forceinline__ void flush_min(uint64_t *__restrict__ best, uint32_t 
 // block instead of one per run — same-address global operations serialise at the memory side
 // (~12 ns each, MI355X_MICROARCH.md "fanin") and atomics drop the line from L2, so every later
 // plain read of that slot misses too.
-// k_filter: issue the random b-probe only for edges whose a-end is in the giant (1), or for
-// every heavy edge beside the a-probes (0)
-// k_resolve: 4 vertices per lane with their label walks interleaved — consecutive (1) or a grid
-// stride apart (2) — or one per thread (0)
-#ifndef GHS_RESOLVE4
-#define GHS_RESOLVE4 1
-#endif
-#ifndef GHS_FILTER_GATED
-#define GHS_FILTER_GATED 1
-#endif
-#ifndef GHS_HOT_BITS
-#define GHS_HOT_BITS 9
-#endif
-constexpr int HOT_BITS = GHS_HOT_BITS;
+constexpr int HOT_BITS = 9;  // 128 / 256 / 1024 slots measured (DESIGN.md "Measured and rejected")
 // the compacting min-edge's parallel-edge filter: LDS pair slots per block,
 // linear probes, and the host's bound on the active fragments below which the filtering variant
 // is launched (it filters when the exact count is <= the solver's dedup_max: env GHS_DEDUP_MAX,
@@ -273,11 +261,8 @@ __device__ __forceinline__ uint4 ld_b128(__amdgpu_buffer_rsrc_t r, uint32_t byte
 // The same as a non-temporal (streaming) load: the canonical list is read once per pass, and
 // default-policy lines of a 3-12 GB stream evict the L2-resident giant bitmap that the pass's
 // random probes need (R-MAT s26: 8 MiB bitmap, 4 MiB L2 per XCD). cache policy bits: nt = 2.
-#ifndef GHS_FILTER_NT
-#define GHS_FILTER_NT 1
-#endif
 __device__ __forceinline__ uint4 ld_b128_nt(__amdgpu_buffer_rsrc_t r, uint32_t byte_off) {
-  const u32x4 x = __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_off, 0, GHS_FILTER_NT ? 2 : 0);
+  const u32x4 x = __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_off, 0, 2);
   return make_uint4(x.x, x.y, x.z, x.w);
 }
 
@@ -1429,10 +1414,7 @@ __device__ __forceinline__ void add_totals(unsigned long long wsum, unsigned lon
 // grid, level 0 rounds 1-3: 2.29 / 1.29 / 0.48 -> 1.85 / 1.17 / 0.43 ms (2 steps; 4 the same).
 // k_jump_ident keeps splitting from the first step: the gradient grid's long hook chains need it
 // (its level-0 jump 1.54 -> 1.83 ms with 2 steps, profiles/r03/ab_split/).
-#ifndef GHS_SPLIT_AFTER
-#define GHS_SPLIT_AFTER 2
-#endif
-constexpr uint32_t SPLIT_AFTER = GHS_SPLIT_AFTER;
+constexpr uint32_t SPLIT_AFTER = 2;
 __global__ __launch_bounds__(BLOCK) void k_jump(const uint32_t *__restrict__ act, const unsigned long long *__restrict__ d_nact,
                                                 uint32_t *par, uint32_t *__restrict__ lab, uint64_t *__restrict__ best,
                                                 uint8_t *__restrict__ flags, unsigned long long *__restrict__ err,
@@ -1693,48 +1675,9 @@ __global__ __launch_bounds__(BLOCK) void k_resolve(uint32_t n, uint32_t *lab, co
                                                    uint64_t *__restrict__ bits, unsigned long long *__restrict__ err) {
   const uint32_t giant = giant_ptr[0];
   const uint64_t words = ((uint64_t)n + 63) / 64;
-#if GHS_RESOLVE4 == 2
-  // 4 vertices per thread a grid stride S apart (their walks start far apart on a chain, as in
-  // k_jump_ident), advanced together; each of the 4 is a coalesced wave slice of 64 vertices, so
-  // the giant bits of slice k are one ballot = one 64-bit bitmap word (S is a multiple of 64)
-  const uint64_t tg = blockIdx.x * (uint64_t)BLOCK + threadIdx.x, S = (uint64_t)gridDim.x * BLOCK;
-  for (uint64_t cb = 0; cb < (uint64_t)n; cb += 4 * S) {
-    uint32_t x[4], y[4], walking = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const uint64_t vv = cb + tg + S * k;
-      x[k] = (uint32_t)vv;
-      y[k] = vv < n ? lab[vv] : (uint32_t)vv;
-      if (vv < n && y[k] != x[k]) walking |= 1u << k;
-    }
-    uint32_t hops = 0;
-    while (walking) {
-      uint32_t ny[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) ny[k] = lab[(walking >> k) & 1u ? y[k] : 0u];  // finished: a harmless load
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        if (!((walking >> k) & 1u)) continue;
-        x[k] = y[k];
-        y[k] = ny[k];
-        if (y[k] == x[k]) walking &= ~(1u << k);
-      }
-      if (++hops > FIND_LAB_MAX_HOPS) {
-        atomicOr(err, 1ull);
-        break;
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const uint64_t vv = cb + tg + S * k;
-      if (vv < n) lab[vv] = x[k];
-      const uint64_t b = __ballot((vv < n) && x[k] == giant);
-      if ((threadIdx.x & (WAVE - 1)) == 0 && (vv >> 6) < words) bits[vv >> 6] = b;
-    }
-  }
-#elif GHS_RESOLVE4
   // 4 vertices per lane (16-B lab load/store), their label walks advanced together; a lane's 4
   // giant bits are OR-combined over 16 lanes into one 64-bit bitmap word
+  // (the 4 a grid stride apart, or one vertex per thread: DESIGN.md "Measured and rejected")
   const uint64_t n4 = (uint64_t)n & ~3ull;
   const uint32_t lane = threadIdx.x & (WAVE - 1);
   for (uint64_t i0 = (blockIdx.x * (uint64_t)BLOCK + threadIdx.x) * 4; i0 - lane * 4 < (uint64_t)n;
@@ -1783,19 +1726,6 @@ __global__ __launch_bounds__(BLOCK) void k_resolve(uint32_t n, uint32_t *lab, co
     for (int d = 1; d < 16; d <<= 1) part |= __shfl_xor(part, d);
     if ((lane & 15) == 0 && (i0 >> 6) < words) bits[i0 >> 6] = part;
   }
-#else
-  for (uint64_t base = blockIdx.x * (uint64_t)BLOCK; base < (uint64_t)n; base += (uint64_t)gridDim.x * BLOCK) {
-    const uint64_t v = base + threadIdx.x;
-    bool in = false;
-    if (v < n) {
-      const uint32_t r = find_lab(lab, (uint32_t)v, err);
-      lab[v] = r;
-      in = r == giant;
-    }
-    const uint64_t b = __ballot(in);
-    if ((threadIdx.x & (WAVE - 1)) == 0 && (v >> 6) < words) bits[v >> 6] = b;
-  }
-#endif
 }
 
 
@@ -1926,13 +1856,7 @@ __global__ __launch_bounds__(1024) void k_plan(const uint32_t *__restrict__ samp
 //    The row costs were measured per pass (R-MAT s24, same box, profiles/r06/csr/): k_select's wave
 //    slices at 2 edges per row (row cost 8) run 0.76 -> 0.58 ms against 0.5 edge (row cost 2), while
 //    k_filter's blocks are best near 0.5 edge per row (1.66 ms; 1.68 at 2 edges, 1.69 at 6).
-#ifndef GHS_CSR_ROW_SEL
-#define GHS_CSR_ROW_SEL 8
-#endif
-#ifndef GHS_CSR_ROW_FIL
-#define GHS_CSR_ROW_FIL 2
-#endif
-constexpr uint64_t CSR_EDGE_COST = 4, CSR_ROW_SEL = GHS_CSR_ROW_SEL, CSR_ROW_FIL = GHS_CSR_ROW_FIL;
+constexpr uint64_t CSR_EDGE_COST = 4, CSR_ROW_SEL = 8, CSR_ROW_FIL = 2;
 // Rb, Re: the rows of the range's first and last edges (one wave: a 64-ary search each), once per
 // solve, before the row pass and the bounds
 __global__ __launch_bounds__(64) void k_csr_range(const uint32_t *__restrict__ off, uint32_t n, uint64_t E0, uint64_t e_hi,
@@ -2173,13 +2097,9 @@ GHS_STREAM_KERNEL_6 void k_select(uint32_t n, uint64_t m, uint64_t e_lo, uint64_
 // edges.
 // ------------------------------------------------------------------------------------------
 // CSR: 70 VGPRs (the row derivation), i.e. 7 blocks per CU, and the grid sized to one residency wave
-// (7 x 256 blocks); 8 waves forced (GHS_FILTER_CSR_W8=1: 62 VGPRs + 4 spilled) measured slower:
-// R-MAT s24 k_filter 1.85 against 1.65 ms, same box)
-#ifndef GHS_FILTER_CSR_W8
-#define GHS_FILTER_CSR_W8 0
-#endif
+// (7 x 256 blocks); 8 waves forced measured slower (DESIGN.md "Measured and rejected")
 template <bool CSR>
-__global__ __launch_bounds__(BLOCK, (CSR && GHS_FILTER_CSR_W8) ? 8 : GHS_STREAM_WAVES) __attribute__((amdgpu_num_sgpr(72))) void k_filter(uint32_t n, uint64_t e_lo, uint64_t e_hi, const uint32_t *__restrict__ eu,
+GHS_STREAM_KERNEL void k_filter(uint32_t n, uint64_t e_lo, uint64_t e_hi, const uint32_t *__restrict__ eu,
                                 const uint32_t *__restrict__ eoff, const uint32_t *__restrict__ trow,
                                 const uint32_t *__restrict__ ev, const uint32_t *__restrict__ ew,
                                 const uint64_t *__restrict__ w_range /* [w_lo, w_hi] */,
@@ -2258,15 +2178,11 @@ __global__ __launch_bounds__(BLOCK, (CSR && GHS_FILTER_CSR_W8) ? 8 : GHS_STREAM_
     const uint4 q0 = bits4[A0];
     const uint4 q3 = bits4[A3];
     uint32_t gbw[4];
-#if !GHS_FILTER_GATED
-#pragma unroll
-    for (int j = 0; j < 4; ++j) gbw[j] = bits32[out[j] ? (b[j] >> 5) : 0u];
-#endif
     uint32_t ga[4], gb[4];
-#if GHS_FILTER_GATED
     // gated b-probes: only an edge whose a-end is in the giant can be dropped, so the random
     // b-probe (one L2 request) is issued for those edges alone, after the a-probes landed (the
     // sequential a-probes are near-always L2 hits); the next tile's stream loads follow them
+    // (a b-probe for every heavy edge beside the a-probes: DESIGN.md "Measured and rejected")
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const uint32_t blk = a[j] >> 7, wsel = (a[j] >> 5) & 3;
@@ -2278,7 +2194,6 @@ __global__ __launch_bounds__(BLOCK, (CSR && GHS_FILTER_CSR_W8) ? 8 : GHS_STREAM_
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) gbw[j] = bits32[(out[j] & (ga[j] != 0u)) ? (b[j] >> 5) : 0u];
-#endif
     // next tile (out-of-range offsets read 0)
     const uint32_t noff = (uint32_t)(v0 + ARCS_PER_BLOCK - vb) * 4u + lane_off;
     if (!CSR) ca = ld_b128_nt(ru, noff);
@@ -2286,19 +2201,7 @@ __global__ __launch_bounds__(BLOCK, (CSR && GHS_FILTER_CSR_W8) ? 8 : GHS_STREAM_
     cw = ld_b128_nt(rw, noff);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-#if !GHS_FILTER_GATED
-      const uint32_t blk = a[j] >> 7, wsel = (a[j] >> 5) & 3;
-      const uint4 q = (blk == A0) ? q0 : q3;
-      const bool odd = wsel & 1;  // two-level select (an == chain becomes a branch tree)
-      const uint32_t lo = odd ? q.y : q.x, hi = odd ? q.w : q.z;
-      const uint32_t word = (wsel & 2) ? hi : lo;
-      ga[j] = ((blk == A0) | (blk == A3)) ? (word >> (a[j] & 31)) & 1u : 0u;
-#endif
-#if GHS_FILTER_GATED
       gb[j] = ga[j] & (gbw[j] >> (b[j] & 31));  // unprobed b: "not known in the giant" (lab gathered)
-#else
-      gb[j] = (gbw[j] >> (b[j] & 31)) & 1u;
-#endif
       out[j] = out[j] & ((ga[j] & gb[j]) == 0u);  // bitwise (no && : keeps the probes unsunk)
     }
     // level-1 split: labels only for this level's edges, and only for ends outside the giant
@@ -2532,20 +2435,13 @@ constexpr uint32_t BK_G = 512;        // k_bucket blocks = record regions
 constexpr uint32_t BK_T = 512;        // k_bucket threads
 constexpr uint32_t BK_MAX_B = 16384;  // buckets: k_bucket's LDS counters (64 KiB)
 constexpr uint32_t BM_T = 1024;       // k_bmin threads
-#ifndef GHS_BK_TILES
-#define GHS_BK_TILES 2
-#endif
-constexpr int BK_TILES = GHS_BK_TILES;  // k_bucket: 4-edge tiles per lane in flight
+constexpr int BK_TILES = 2;           // k_bucket: 4-edge tiles per lane in flight
 
 // The offsets table of a bucketed round, (nb + 1) x BK_G words. Block-major (region g's nb + 1
 // offsets contiguous: k_bucket writes its row with coalesced stores; k_bmin's workgroup t reads one
-// word per region) — GHS_BK_BLOCKMAJOR=0: bucket-major (a bucket's 512 offsets contiguous: k_bmin
-// reads one row, but every k_bucket block writes a strided column, nb + 1 scattered 4-B stores).
-#ifndef GHS_BK_BLOCKMAJOR
-#define GHS_BK_BLOCKMAJOR 1
-#endif
+// word per region); bucket-major made every k_bucket block write a strided column.
 __device__ __forceinline__ uint64_t bk_off_index(uint32_t t, uint32_t g, uint32_t nb) {
-  return GHS_BK_BLOCKMAJOR ? (uint64_t)g * (nb + 1) + t : (uint64_t)t * BK_G + g;
+  return (uint64_t)g * (nb + 1) + t;
 }
 
 // a block's share of the T live edges (a multiple of 4: whole 4-entry tiles); region g of the
@@ -2756,13 +2652,7 @@ __global__ __launch_bounds__(BK_T) void k_bucket(const uint32_t *__restrict__ sr
 // k_bmin: BM_ILP records in flight per lane; the bucket's non-empty runs listed first (a lattice
 // bucket's records come from one to three block regions), so locating a record searches that
 // short list
-#ifndef GHS_BM_ILP
-#define GHS_BM_ILP 8
-#endif
-constexpr int BM_ILP = GHS_BM_ILP;
-#ifndef GHS_BM_COMPRESS
-#define GHS_BM_COMPRESS 1
-#endif
+constexpr int BM_ILP = 8;
 
 // The LDS core of a bucketed round (k_bmin over records, k_wmin over a window of the level's edge
 // list): `sweep(f)` calls f(a, b, key) for every candidate edge of bucket t (block-wide: every
@@ -2829,7 +2719,6 @@ __device__ __forceinline__ void bucket_round(uint32_t t, unsigned long long *s_m
   // only move to ancestors, so concurrent updates are safe. par then points at the first
   // ancestor outside the bucket, the in-bucket root, or a member of a cross-bucket pair.
   auto in_bucket = [&](uint64_t v) -> bool { return (uint32_t)v == (uint32_t)TAG && ((uint32_t)(v >> 32) >> BS) == t; };
-  if (GHS_BM_COMPRESS) {
   for (uint32_t i = threadIdx.x; i < SPAN; i += BM_T) {
     const uint64_t v = s_min[i];
     if (!in_bucket(v)) continue;
@@ -2850,7 +2739,6 @@ __device__ __forceinline__ void bucket_round(uint32_t t, unsigned long long *s_m
     }
     if (!__syncthreads_or(more)) break;  // one barrier: every thread sees the same answer
   }
-  }  // GHS_BM_COMPRESS
   for (uint32_t i = threadIdx.x; i < SPAN; i += BM_T) {
     const uint64_t v = s_min[i];
     if ((uint32_t)v == (uint32_t)TAG) par[tb + i] = (uint32_t)(v >> 32);
@@ -3017,10 +2905,6 @@ __global__ __launch_bounds__(256) void k_wstarts(SegView in, const uint32_t *__r
 }
 
 constexpr uint32_t WM_CHUNK = 32;
-#ifndef GHS_WM_GATHER
-#define GHS_WM_GATHER 1
-#endif
-constexpr bool WM_GATHER = GHS_WM_GATHER;  // k_wmin: winners from the canonical ends (bucket_round)
 template <uint32_t BS>
 __global__ __launch_bounds__(BM_T) void k_wmin(const uint32_t *__restrict__ src, const uint32_t *__restrict__ dst,
                                                const uint64_t *__restrict__ key, SegView in, uint32_t nb,
@@ -3607,548 +3491,7 @@ __global__ __launch_bounds__(BLOCK) void k_select_lb(const uint8_t *__restrict__
   }
 }
 
-// ------------------------------------------------------------------------------------------
-// The LDS tail of a level (one rank). Once a level's active fragments fit a workgroup's LDS
-// (<= TAIL_MAX), its remaining rounds — the reference's last TEST / REPORT / CHANGEROOT /
-// INITIATE exchanges of a level, ghs_implementation.py:235-387 — run without any global atomic and
-// without n-sized arrays: the fragments get dense ids 0..F0-1 (their order in the active list),
-// every edge is relabelled ONCE to the dense pair of its fragments, and each later round keeps
-// every root's minimum in LDS per block.
-//   k_tail_map    dmap[act[i]] = i; the tail's control block, R = identity, the root list
-//   k_tail_open   (round 0 of the tail) every live edge: a, b -> dmap (its dense fragments);
-//                 intra-fragment edges dropped, the rest compacted in order to the block's region of
-//                 the tail buffer as one 12-byte record (da | db << 16, key); each end's candidate
-//                 min'ed into the block's LDS minima; the block's row: each minimum's key and other end
-//   k_tail_hook   one slot per active root: the minimum over the blocks' rows and its other end
-//                 (the CONNECT target), the MSF flag of the edge
-//   k_tail_round  every block applies the last round's hooks in LDS — over the ROOTS only: mutual
-//                 pairs keep the smaller root, pointer jumping among the roots, then every dense id's
-//                 root through one lookup (R[d] = P[R[d]]), the next root list — identically in every
-//                 block (no grid barrier: the launch boundaries order open -> hook -> round -> hook,
-//                 so ranks sharing a device cannot deadlock it), then streams its records (a
-//                 candidate only where R[da] != R[db]) into its LDS minima and row. A round that
-//                 starts with <= 1 active root finishes the level instead: lab of every fragment of
-//                 the level = its final root, the round report.
-// The LDS minima carry (w << 32 | the record's index in the block's region) instead of the key:
-// a block's region holds its records in canonical (eid) order — a level's live edges keep the
-// canonical order within and across their regions (k_select / k_filter / k_level_pass emit it,
-// every compaction keeps it) and the open compacts in order — so within a block that order IS the
-// (w, eid) order, and each minimum's record is one load away: its true key for the row and its
-// other end. (Round 4's hook found the other end through the canonical list and the label chains,
-// and its prologue jumped pointers over all F0 dense ids.)
-// Per round: one stream of the 12-byte records + two launch boundaries, instead of the round
-// kernels' relabel gathers, LDS-cache misses to best[], hook, jump and select over n-sized arrays.
-// ------------------------------------------------------------------------------------------
-constexpr uint32_t TAIL_MAX = 12288;        // dense fragments: LDS minima 96 KiB + 2 x 24 KiB of u16 tables
-constexpr uint32_t TAIL_T = 1024;           // threads of the streaming tail kernels (16 waves, 1 block per CU)
-constexpr uint32_t TAIL_G = 256;            // their blocks = rows of `partial`
-constexpr uint32_t TAIL_ROUNDS_MAX = 32;    // a tail round at least halves the roots: <= 14 rounds
-constexpr uint32_t TAIL_HS = 16;            // k_tail_hook: slots per 256-thread block (16 row groups)
-constexpr uint16_t TAIL_NONE = 0xffffu;     // a row's other end where the block has no candidate
-static_assert(TAIL_MAX <= 32768, "dense ids are packed as 16-bit pairs");
-
-struct TailCtl {
-  uint32_t F0;        // dense fragments (the active list at the tail's start)
-  uint32_t done;      // the level is complete (lab written)
-  uint32_t rounds;    // tail rounds streamed (set when done)
-  uint32_t err;
-  uint64_t Q;         // each block's region stride in the tail buffer
-  uint64_t nroots[TAIL_ROUNDS_MAX + 1];  // active roots of round r (its list: droot[r & 1])
-  uint64_t live[TAIL_ROUNDS_MAX];        // live (inter-fragment) edges round r scanned
-  uint64_t edges[TAIL_ROUNDS_MAX];       // MSF edges (C_EDGES) once round r's hooks are counted
-};
-
-struct TailBufs {
-  TailCtl *ctl;
-  uint32_t *dmap;      // root label -> dense id (n entries; only the tail's roots are meaningful)
-  uint64_t *partial;   // TAIL_G rows x TAIL_MAX block minima (root-list order)
-  uint16_t *poth;      // ... and each minimum's other end (dense root id at the time of the stream)
-  uint32_t *R[2];      // dense id -> dense root during round r: R[r & 1]
-  uint32_t *droot[2];  // round r's active roots (ascending dense ids): droot[r & 1]
-  uint32_t *ghook;     // per dense root: CONNECT target (dense root) of its minimum edge
-  uint64_t *gkey;      // per dense root: its minimum key (KEY_NONE: no outgoing edge)
-  uint64_t *gloc;      // several ranks: this rank's own minimum (gkey is then MIN-all-reduced)
-  uint32_t *blive;     // per block: live edges of the round it streamed
-  uint32_t *bcnt;      // per block: records in its region of the tail buffer
-  uint32_t *rec;       // the tail buffer: da | db << 16
-  uint64_t *rkey;      //   ... and the key
-};
-
-// A tail in progress (run_tail's batches, or the stepwise ghs_solver_tail_* calls of several ranks)
-struct TailRun {
-  TailBufs tb{};
-  const uint32_t *act0 = nullptr;
-  uint32_t F0 = 0, round0 = 0, lr0 = 0, r = 1;  // r: the next tail round to stream
-  unsigned hook_g = 1;
-  bool multi = false;
-};
-
-__global__ void k_tail_map(const uint32_t *__restrict__ act, const unsigned long long *__restrict__ d_nact, TailBufs tb) {
-  const uint32_t F = (uint32_t)*d_nact;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < F; i += gridDim.x * blockDim.x) {
-    tb.dmap[act[i]] = i;
-    tb.R[0][i] = i;
-    tb.droot[0][i] = i;
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    TailCtl *c = tb.ctl;
-    c->F0 = F;
-    c->done = 0;
-    c->rounds = 0;
-    c->err = 0;
-    c->nroots[0] = F;
-  }
-}
-
-// The labels the live edges carry (the previous round's active list, or every vertex after a
-// level's identity round) -> the dense id of their fragment now: dmap[x] = dmap[lab[x]] (one hop:
-// lab of those labels is current; a root's own entry is k_tail_map's and is not rewritten here),
-// so k_tail_open relabels an end with ONE gather.
-__global__ void k_tail_labels(const uint32_t *__restrict__ prev, const unsigned long long *__restrict__ d_nprev,
-                              const uint32_t *__restrict__ lab, TailBufs tb) {
-  const uint64_t np = *d_nprev;
-  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < np; i += (uint64_t)gridDim.x * blockDim.x) {
-    const uint32_t x = prev ? prev[i] : (uint32_t)i;
-    const uint32_t l = lab[x];
-    if (l != x) tb.dmap[x] = tb.dmap[l];
-  }
-}
-
-__device__ __forceinline__ void lds_min_u64(unsigned long long *s, uint32_t i, uint64_t k) {
-  if (k < s[i]) atomicMin(&s[i], (unsigned long long)k);  // a plain read first: slots only decrease
-}
-
-// a wave's survivors staged in LDS for coalesced stores (12-byte records)
-struct TailStage {
-  uint32_t p[WAVE * 4];
-  uint64_t k[WAVE * 4];
-};
-
-// a block-local candidate: the key's weight with the record's index in the block's region (the
-// region is in eid order, so this orders the block's candidates exactly as (w, eid))
-__device__ __forceinline__ uint64_t tail_local(uint64_t key, uint32_t idx) { return (key & ~0xffffffffull) | idx; }
-
-// The block's row (root-list order: root i of the round = droots[i]): each root's minimum
-// record (one load: its index is in the LDS minimum) gives the true key and the other end's dense
-// root (through R: rmap == nullptr is the identity, the open). Every record load in flight first.
-__device__ __forceinline__ void tail_row_out(const TailBufs tb, const unsigned long long *s_best, const uint16_t *droots,
-                                             uint32_t nroot, const uint32_t *__restrict__ pr, const uint64_t *__restrict__ pk,
-                                             const uint16_t *rmap) {
-  constexpr uint32_t PER = TAIL_MAX / TAIL_T;
-  uint64_t *row = tb.partial + (uint64_t)blockIdx.x * TAIL_MAX;
-  uint16_t *orow = tb.poth + (uint64_t)blockIdx.x * TAIL_MAX;
-  uint32_t p[PER], d[PER];
-  uint64_t k[PER];
-#pragma unroll
-  for (uint32_t q = 0; q < PER; ++q) {
-    const uint32_t i = threadIdx.x + q * TAIL_T;
-    d[q] = i < nroot ? (droots ? droots[i] : i) : 0u;
-    const uint64_t v = i < nroot ? s_best[d[q]] : KEY_NONE;
-    const bool has = v != KEY_NONE;
-    p[q] = has ? pr[(uint32_t)v] : 0u;
-    k[q] = has ? pk[(uint32_t)v] : KEY_NONE;
-  }
-#pragma unroll
-  for (uint32_t q = 0; q < PER; ++q) {
-    const uint32_t i = threadIdx.x + q * TAIL_T;
-    if (i >= nroot) break;
-    uint16_t o = TAIL_NONE;
-    if (k[q] != KEY_NONE) {
-      const uint32_t da = p[q] & 0xffffu, db = p[q] >> 16;
-      const uint32_t ra = rmap ? rmap[da] : da, rb = rmap ? rmap[db] : db;
-      o = (uint16_t)(ra == d[q] ? rb : ra);
-    }
-    row[i] = k[q];
-    orow[i] = o;
-  }
-}
-
-// check (GHS_OPT_CHECK_TOTALS): verify the invariant the (w, index) minima rest on — the
-// block's region holds its records in strictly increasing eid order — after writing it
-__global__ __launch_bounds__(TAIL_T) void k_tail_open(const uint32_t *__restrict__ src, const uint32_t *__restrict__ dst,
-                                                      const uint64_t *__restrict__ key, SegView in, TailBufs tb,
-                                                      bool check) {
-  __shared__ unsigned long long s_best[TAIL_MAX];
-  __shared__ TailStage s_stage[TAIL_T / WAVE];
-  __shared__ uint32_t s_wcnt[TAIL_T / WAVE];
-  __shared__ uint32_t s_seg[2];
-  __shared__ uint32_t s_live;
-  const uint32_t F = tb.ctl->F0;
-  for (uint32_t i = threadIdx.x; i < F; i += TAIL_T) s_best[i] = KEY_NONE;
-  const uint64_t T = in.prefix[in.nseg];
-  const uint64_t Q = ((T + gridDim.x - 1) / gridDim.x + 3) & ~3ull;
-  const uint64_t vb = Q * blockIdx.x;
-  const uint64_t ve = (vb + Q < T) ? vb + Q : T;
-  if (threadIdx.x < WAVE) seg_range_wave(in.prefix, in.nseg, vb, ve, T, s_seg);
-  if (threadIdx.x == 0) {
-    s_live = 0;
-    if (blockIdx.x == 0) tb.ctl->Q = Q;
-  }
-  __syncthreads();
-  const uint32_t slo = s_seg[0], shi = s_seg[1];
-  const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-  uint32_t *orec = tb.rec + vb;
-  uint64_t *okey = tb.rkey + vb;
-  constexpr uint64_t STEP = (uint64_t)TAIL_T * 4;
-  uint32_t out_n = 0, live_n = 0;
-  for (uint64_t v0 = vb; v0 < ve; v0 += STEP) {
-    const uint64_t v = v0 + (uint64_t)threadIdx.x * 4;
-    const bool in_range = v < ve;
-    const uint64_t ph = tile_phys(in, slo, shi, v, ve);
-    const uint4 a4 = *reinterpret_cast<const uint4 *>(src + ph), b4 = *reinterpret_cast<const uint4 *>(dst + ph);
-    const ulonglong2 k01 = *reinterpret_cast<const ulonglong2 *>(key + ph),
-                     k23 = *reinterpret_cast<const ulonglong2 *>(key + ph + 2);
-    const uint32_t A[4] = {a4.x, a4.y, a4.z, a4.w}, B[4] = {b4.x, b4.y, b4.z, b4.w};
-    const uint64_t K[4] = {k01.x, k01.y, k23.x, k23.y};
-    uint32_t da[4], db[4], mask = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {  // the dense fragments now (k_tail_labels: one gather per end)
-      const bool valid = in_range & (A[j] != LABEL_NONE);
-      da[j] = tb.dmap[valid ? A[j] : 0u];
-      db[j] = tb.dmap[valid ? B[j] : 0u];
-      mask |= (valid & (da[j] != db[j])) ? (1u << j) : 0u;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (((mask >> j) & 1u) && (da[j] >= F || db[j] >= F)) {  // a live edge must join two active fragments
-        atomicOr(&tb.ctl->err, 1u);
-        mask &= ~(1u << j);
-      }
-    live_n += __popc(mask);
-    // survivors -> this block's region of the tail buffer, in order; their candidates carry their index
-    uint32_t lane_excl, wave_before, wave_cnt, total;
-    block_offsets_w<TAIL_T>((uint32_t)__popc(mask), s_wcnt, &lane_excl, &wave_before, &wave_cnt, &total);
-    TailStage &ws = s_stage[wid];
-    uint32_t o = lane_excl;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if ((mask >> j) & 1u) {
-        ws.p[o] = da[j] | (db[j] << 16);
-        ws.k[o] = K[j];
-        const uint64_t c = tail_local(K[j], out_n + wave_before + o);
-        lds_min_u64(s_best, da[j], c);
-        lds_min_u64(s_best, db[j], c);
-        ++o;
-      }
-    wave_sync_lds();  // the wave's records leave LDS as consecutive stores
-    for (uint32_t i = lane; i < wave_cnt; i += WAVE) {
-      orec[out_n + wave_before + i] = ws.p[i];
-      okey[out_n + wave_before + i] = ws.k[i];
-    }
-    wave_sync_lds();
-    out_n += total;
-  }
-  for (int d = WAVE / 2; d > 0; d >>= 1) live_n += __shfl_xor(live_n, d);
-  if ((threadIdx.x & (WAVE - 1)) == 0) atomicAdd(&s_live, live_n);
-  __syncthreads();  // every wave's record stores drained: the row reads them back through L2
-  if (check)
-    for (uint32_t i = threadIdx.x + 1; i < out_n; i += TAIL_T)
-      if ((uint32_t)okey[i - 1] >= (uint32_t)okey[i]) atomicOr(&tb.ctl->err, 1u);
-  // the block's minima of every dense fragment (round 0: the root list is the identity)
-  tail_row_out(tb, s_best, nullptr, F, orec, okey, nullptr);
-  if (threadIdx.x == 0) {
-    tb.bcnt[blockIdx.x] = out_n;
-    tb.blive[blockIdx.x] = s_live;
-  }
-}
-
-// One active root per slot (root-list order): the blocks' minima reduced (16 row groups per slot)
-// with their other ends, the root's CONNECT target, its MSF flag. Block 0 also totals the
-// streamed round's live edges.
-// several ranks (multi): the minimum is this rank's only — kept in gloc as well, no MSF flag yet
-// (k_tail_xhook writes it once the ranks agree on the minimum)
-__global__ __launch_bounds__(256) void k_tail_hook(TailBufs tb, uint32_t r, uint8_t *__restrict__ in_mst,
-                                                   uint32_t nblocks, unsigned long long *__restrict__ err,
-                                                   bool multi) {
-  __shared__ unsigned long long s_part[256];
-  __shared__ uint32_t s_prow[256];
-  TailCtl *c = tb.ctl;
-  if (c->done) return;  // r: the round just streamed
-  const uint32_t nroot = (uint32_t)c->nroots[r];
-  if (blockIdx.x == 0 && threadIdx.x < WAVE) {
-    uint64_t t = 0;
-    for (uint32_t b = threadIdx.x; b < nblocks; b += WAVE) t += tb.blive[b];
-    for (int d = WAVE / 2; d > 0; d >>= 1) t += __shfl_xor(t, d);
-    if (threadIdx.x == 0) c->live[r] = t;
-  }
-  const uint32_t s = threadIdx.x % TAIL_HS, g = threadIdx.x / TAIL_HS;  // slot, row group
-  const uint32_t i = blockIdx.x * TAIL_HS + s;
-  if (blockIdx.x * TAIL_HS >= nroot) return;  // block-uniform
-  constexpr uint32_t GROUPS = 256 / TAIL_HS;
-  uint64_t m = KEY_NONE;
-  uint32_t w = 0;
-  if (i < nroot) {
-    uint64_t x[TAIL_G / GROUPS];
-#pragma unroll
-    for (uint32_t k = 0; k < TAIL_G / GROUPS; ++k) {
-      const uint32_t b = g + k * GROUPS;
-      x[k] = b < nblocks ? tb.partial[(uint64_t)b * TAIL_MAX + i] : KEY_NONE;
-    }
-#pragma unroll
-    for (uint32_t k = 0; k < TAIL_G / GROUPS; ++k)
-      if (x[k] < m) {
-        m = x[k];
-        w = g + k * GROUPS;
-      }
-  }
-  s_part[threadIdx.x] = m;
-  s_prow[threadIdx.x] = w;
-  __syncthreads();
-  if (g != 0 || i >= nroot) return;
-  for (uint32_t k = 1; k < GROUPS; ++k) {
-    const uint64_t x = s_part[k * TAIL_HS + s];
-    if (x < m) {
-      m = x;
-      w = s_prow[k * TAIL_HS + s];
-    }
-  }
-  const uint32_t d = tb.droot[r & 1][i];
-  uint32_t o = LABEL_NONE;
-  if (m != KEY_NONE) {
-    o = tb.poth[(uint64_t)w * TAIL_MAX + i];
-    if (o >= c->F0 || o == d) {  // the minimum edge must leave root d towards another root
-      atomicOr(err, 2ull);
-      o = LABEL_NONE;
-      m = KEY_NONE;
-    } else if (!multi) {
-      in_mst[(uint32_t)m] = 1;  // both members of a mutual pair mark the same edge
-    }
-  }
-  tb.gkey[d] = m;
-  tb.ghook[d] = o;
-  if (multi) tb.gloc[d] = m;
-}
-
-// Several ranks, between the MIN all-reduce of gkey and the MAX all-reduce of ghook: a root whose
-// global minimum is this rank's own keeps its CONNECT target (and the owner writes the MSF flag of
-// its own edge); every other root's target is withdrawn (LABEL_NONE = -1 under the int32 MAX), so
-// the all-reduce leaves the owner's target on every rank. Keys are (w << 32 | global eid): unique.
-__global__ __launch_bounds__(256) void k_tail_xhook(TailBufs tb, uint32_t r, uint8_t *__restrict__ in_mst,
-                                                    uint32_t e_lo, uint32_t e_hi) {
-  const TailCtl *c = tb.ctl;
-  if (c->done) return;
-  const uint32_t nroot = (uint32_t)c->nroots[r];
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nroot; i += gridDim.x * blockDim.x) {
-    const uint32_t d = tb.droot[r & 1][i];
-    const uint64_t g = tb.gkey[d];
-    if (g != KEY_NONE && g == tb.gloc[d]) {
-      const uint32_t eid = (uint32_t)g;
-      if (eid >= e_lo && eid < e_hi) in_mst[eid] = 1;
-    } else {
-      tb.ghook[d] = LABEL_NONE;
-    }
-  }
-}
-
-// Every block applies the last round's hooks (identical LDS computation in every block, over the
-// roots only), then streams its records — or, when <= 1 root stays active, block 0 finishes the level.
-__global__ __launch_bounds__(TAIL_T) void k_tail_round(TailBufs tb, uint32_t r, const uint32_t *__restrict__ act0,
-                                                       uint32_t *__restrict__ lab, unsigned long long *__restrict__ cnt,
-                                                       unsigned long long *__restrict__ err) {
-  __shared__ unsigned long long s_best[TAIL_MAX];  // the prologue's pointer table first (u32 view)
-  __shared__ uint16_t s_R[TAIL_MAX];
-  __shared__ uint16_t s_root[TAIL_MAX];
-  __shared__ uint32_t s_wsum[TAIL_T / WAVE];
-  __shared__ unsigned long long s_tw, s_tc;
-  __shared__ uint32_t s_live;
-  TailCtl *c = tb.ctl;
-  if (c->done) return;
-  const uint32_t F = c->F0;  // r: the round about to stream (round r - 1 hooked last)
-  const uint32_t nprev = (uint32_t)c->nroots[r - 1];
-  const uint32_t *prev = tb.droot[(r - 1) & 1];
-  uint32_t *P = reinterpret_cast<uint32_t *>(s_best);  // dense pointer forest over the roots (prologue only)
-  constexpr uint32_t MARK = 0x80000000u;
-  if (threadIdx.x == 0) {
-    s_tw = 0;
-    s_tc = 0;
-    s_live = 0;
-  }
-  // every global load of the prologue first: the dense ids' roots, the roots' hooks and keys
-  constexpr uint32_t PER = TAIL_MAX / TAIL_T;
-  const uint32_t *Rp = tb.R[(r - 1) & 1];
-  uint32_t rr[PER], pd[PER], ph[PER];
-  uint64_t pk[PER];
-#pragma unroll
-  for (uint32_t q = 0; q < PER; ++q) {
-    const uint32_t d = threadIdx.x + q * TAIL_T, i = d;
-    rr[q] = d < F ? Rp[d] : 0u;
-    pd[q] = i < nprev ? prev[i] : 0u;
-  }
-#pragma unroll
-  for (uint32_t q = 0; q < PER; ++q) {
-    const uint32_t i = threadIdx.x + q * TAIL_T;
-    ph[q] = i < nprev ? tb.ghook[pd[q]] : LABEL_NONE;
-    pk[q] = i < nprev ? tb.gkey[pd[q]] : KEY_NONE;
-  }
-  // every dense id a root of itself (an inactive root of round r - 1 stays one), then the hooks of
-  // round r - 1's active roots
-  for (uint32_t d = threadIdx.x; d < F; d += TAIL_T) P[d] = d;
-  __syncthreads();
-#pragma unroll
-  for (uint32_t q = 0; q < PER; ++q) {
-    const uint32_t i = threadIdx.x + q * TAIL_T;
-    if (i < nprev && ph[q] != LABEL_NONE) P[pd[q]] = ph[q];
-  }
-  __syncthreads();
-  // a mutual pair (d <-> o over their shared minimum) keeps its smaller member as the root
-#pragma unroll
-  for (uint32_t q = 0; q < PER; ++q) {
-    const uint32_t i = threadIdx.x + q * TAIL_T;
-    if (i < nprev) {
-      const uint32_t d = pd[q], o = P[d] & ~MARK;
-      if (o != d && (P[o] & ~MARK) == d && d < o) atomicOr(&P[d], MARK);
-    }
-  }
-  __syncthreads();
-  unsigned long long tw = 0, tc = 0;
-#pragma unroll
-  for (uint32_t q = 0; q < PER; ++q) {
-    const uint32_t i = threadIdx.x + q * TAIL_T;
-    if (i < nprev) {
-      const uint32_t d = pd[q];
-      if (P[d] & MARK) {
-        P[d] = d;
-      } else if (P[d] != d) {  // d hooked: one MSF edge
-        tw += pk[q] >> 32;
-        tc += 1;
-      }
-    }
-  }
-  __syncthreads();
-  for (int it = 0; it < 32; ++it) {  // pointer jumping among the roots (a hook targets a root)
-    int more = 0;
-#pragma unroll
-    for (uint32_t q = 0; q < PER; ++q) {
-      const uint32_t i = threadIdx.x + q * TAIL_T;
-      if (i < nprev) {
-        const uint32_t d = pd[q], p = P[d], pp = P[p];
-        if (pp != p) {
-          P[d] = pp;
-          more = 1;
-        }
-      }
-    }
-    if (!__syncthreads_or(more)) break;
-  }
-  // every dense id's root: its round r - 1 root's final root (a root that was not active keeps itself)
-#pragma unroll
-  for (uint32_t q = 0; q < PER; ++q) {
-    const uint32_t d = threadIdx.x + q * TAIL_T;
-    if (d < F) s_R[d] = (uint16_t)P[rr[q]];
-  }
-  // next roots: round r - 1's roots that had an edge and stayed roots (ascending: a block scan)
-  uint32_t keep = 0;
-#pragma unroll
-  for (uint32_t q = 0; q < PER; ++q) {
-    const uint32_t i = threadIdx.x + q * TAIL_T;
-    if (i < nprev && pk[q] != KEY_NONE && P[pd[q]] == pd[q]) keep |= 1u << q;
-  }
-  uint32_t nroot = 0;
-#pragma unroll
-  for (uint32_t q = 0; q < PER; ++q) {  // root-list order = prev order (chunks of TAIL_T)
-    if (q * TAIL_T < nprev) {  // block-uniform
-      uint32_t tot;
-      const uint32_t k = (keep >> q) & 1u;
-      const uint32_t before = block_excl_scan<TAIL_T>(k, s_wsum, &tot);
-      if (k) s_root[nroot + before] = (uint16_t)pd[q];
-      nroot += tot;
-    }
-  }
-  for (int dd = WAVE / 2; dd > 0; dd >>= 1) {
-    tw += __shfl_xor(tw, dd);
-    tc += __shfl_xor(tc, dd);
-  }
-  if ((threadIdx.x & (WAVE - 1)) == 0 && tc) {
-    atomicAdd(&s_tw, tw);
-    atomicAdd(&s_tc, tc);
-  }
-  __syncthreads();
-  if (blockIdx.x == 0) {
-    if (threadIdx.x == 0) {
-      if (s_tc) {
-        (void)atomicAdd(cnt + 2, s_tw);  // C_WEIGHT, C_EDGES (returning: complete before the report)
-        (void)atomicAdd(cnt + 3, s_tc);
-      }
-      const unsigned long long edges = __hip_atomic_load(cnt + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      c->edges[r - 1] = edges;
-    }
-    if (nroot <= 1 || r >= TAIL_ROUNDS_MAX) {
-      // the level is complete: every fragment of the level takes its final root's label
-      uint32_t xs[PER], roots[PER];
-#pragma unroll
-      for (uint32_t q = 0; q < PER; ++q) {  // every gather in flight, then the stores
-        const uint32_t d = threadIdx.x + q * TAIL_T;
-        xs[q] = d < F ? act0[d] : 0u;
-        roots[q] = d < F ? act0[s_R[d]] : 0u;
-      }
-#pragma unroll
-      for (uint32_t q = 0; q < PER; ++q) {
-        const uint32_t d = threadIdx.x + q * TAIL_T;
-        if (d < F && roots[q] != xs[q]) lab[xs[q]] = roots[q];
-      }
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        if (r >= TAIL_ROUNDS_MAX && nroot > 1) atomicOr(err, 4ull);
-        if (c->err) atomicOr(err, 2ull);
-        c->done = 1;
-        c->rounds = r;
-        cnt[0] = 0;  // C_LIVE: no live edge left in the level
-      }
-      return;
-    }
-    for (uint32_t d = threadIdx.x; d < F; d += TAIL_T) tb.R[r & 1][d] = s_R[d];
-    for (uint32_t i = threadIdx.x; i < nroot; i += TAIL_T) tb.droot[r & 1][i] = s_root[i];
-    if (threadIdx.x == 0) c->nroots[r] = nroot;
-  }
-  if (nroot <= 1 || r >= TAIL_ROUNDS_MAX) return;  // block 0 finishes the level
-  // stream this block's records into the LDS minima of the current roots
-  for (uint32_t i = threadIdx.x; i < nroot; i += TAIL_T) s_best[s_root[i]] = KEY_NONE;
-  __syncthreads();
-  const uint64_t base = c->Q * blockIdx.x;
-  const uint32_t n = tb.bcnt[blockIdx.x];
-  const uint32_t *pr = tb.rec + base;
-  const uint64_t *prk = tb.rkey + base;
-  uint32_t live_n = 0;
-  for (uint32_t e0 = threadIdx.x * 4; e0 < n; e0 += TAIL_T * 4) {
-    uint32_t p[4];
-    uint64_t k[4];
-    if (e0 + 4 <= n) {  // a region starts at a multiple of 4: 16-B aligned
-      const uint4 qv = *reinterpret_cast<const uint4 *>(pr + e0);
-      const ulonglong2 k01 = *reinterpret_cast<const ulonglong2 *>(prk + e0), k23 = *reinterpret_cast<const ulonglong2 *>(prk + e0 + 2);
-      p[0] = qv.x; p[1] = qv.y; p[2] = qv.z; p[3] = qv.w;
-      k[0] = k01.x; k[1] = k01.y; k[2] = k23.x; k[3] = k23.y;
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        p[j] = e0 + j < n ? pr[e0 + j] : 0u;
-        k[j] = e0 + j < n ? prk[e0 + j] : KEY_NONE;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (e0 + j >= n) continue;
-      const uint32_t ra = s_R[p[j] & 0xffffu], rb = s_R[p[j] >> 16];
-      if (ra == rb) continue;
-      ++live_n;
-      const uint64_t cand = tail_local(k[j], e0 + j);
-      lds_min_u64(s_best, ra, cand);
-      lds_min_u64(s_best, rb, cand);
-    }
-  }
-  for (int dd = WAVE / 2; dd > 0; dd >>= 1) live_n += __shfl_xor(live_n, dd);
-  if ((threadIdx.x & (WAVE - 1)) == 0) atomicAdd(&s_live, live_n);
-  __syncthreads();
-  tail_row_out(tb, s_best, s_root, nroot, pr, prk, s_R);
-  if (threadIdx.x == 0) tb.blive[blockIdx.x] = s_live;
-}
-
-// the report of a batch of tail rounds (enqueued after its copy of the control block): nact_out 0
-// when the level is complete, else the active roots of the last round streamed (more rounds follow)
-__global__ void k_tail_report(const TailBufs tb, uint32_t last, RoundSlot *slot, unsigned long long seq,
-                              unsigned long long *cnt) {
-  const TailCtl *c = tb.ctl;
-  write_report(slot, seq, cnt, c->done ? 0ull : (unsigned long long)c->nroots[last], c->F0);
-}
+#include "boruvka/tail.h"  // the LDS tail of a level, device side: TailCtl ... k_tail_report
 
 
 static inline unsigned grid_for(uint64_t items, uint64_t per_block, unsigned cap) {
@@ -4164,12 +3507,9 @@ static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; 
 // in blocks per CU x the CUs), at most cap. A fixed grid past it runs a second, nearly empty wave of
 // blocks at the end: k_select sits at 7 blocks per CU (its SGPRs) and k_level_pass at 6 (its VGPRs),
 // so their 2048-block grids left 256 / 512 blocks to run alone after the rest. Cached per kernel
-// and device (one occupancy query each).
-#ifndef GHS_RESIDENT_GRIDS
-#define GHS_RESIDENT_GRIDS 0
-#endif
-static unsigned resident_grid(const void *kernel, unsigned block, unsigned cap, bool on = GHS_RESIDENT_GRIDS) {
-  if (!on) return cap;
+// and device (one occupancy query each). Only the CSR k_filter's grid is sized by it (open_level);
+// k_select and k_level_pass keep their fixed grids.
+static unsigned resident_grid(const void *kernel, unsigned block, unsigned cap) {
   static std::mutex mu;
   static std::unordered_map<uint64_t, unsigned> cache;
   int dev = 0;
@@ -4384,7 +3724,7 @@ struct ghs_solver {
   bool words_merged = false;                       // this level's flags arrived as merged words
   bool rank_ready = false;                         // ... and the rank tables are built from them
   uint32_t *drank_wpre = nullptr, *drank_cpre = nullptr;
-  uint4 *drank_pk = nullptr;  // the packed rank table (k_rank_pack; GHS_DENSE_PACK)
+  uint4 *drank_pk = nullptr;  // the packed rank table (k_rank_pack)
   uint64_t *dbest = nullptr;
   uint32_t *vlab = nullptr, *vpar = nullptr;
   uint64_t *flag_bits = nullptr;  // the packed level-open flags (ghs_solver_flag_bits)
@@ -4594,10 +3934,7 @@ static bool bucket_geometry(uint32_t n, uint32_t *bs, uint32_t *nb) {
 // the hooks read at the same index — would sit at power-of-two distances and land in the same
 // memory channels. 16384^2 grid, same box (profiles/r05/ab/stagger/): k_jump_ident 4.25 -> 4.00 ms,
 // the step 37.5 -> 37.25 ms (2 repeats each; a 20.6-KiB stagger gave the same jump).
-#ifndef GHS_WS_STAGGER
-#define GHS_WS_STAGGER ((1u << 20) + 1024u)
-#endif
-constexpr size_t WS_STAGGER = GHS_WS_STAGGER;
+constexpr size_t WS_STAGGER = (1u << 20) + 1024u;
 static size_t workspace_layout(uint32_t n, uint64_t m, uint64_t local_edges, ghs_solver *s, char *base) {
   size_t off = 0;
   // only the vertex-sized arrays (read at the same index by the jumps and hooks) are staggered
@@ -4873,15 +4210,14 @@ static int open_level(ghs_solver *s, bool async_open = false) {
   if (first) {
     // SELECT over the canonical list: level-0 edges only (validates the list)
     auto sel = s->csr ? k_select<true> : k_select<false>;
-    G = grid_for(TC, ARCS_PER_BLOCK, resident_grid((const void *)sel, BLOCK, s->seg_g));
+    G = grid_for(TC, ARCS_PER_BLOCK, s->seg_g);
     if (TC) {
       if (s->csr) {
         // CSR: every 256-edge tile's row, the offsets' validation, and both passes' cost-balanced
         // partitions (k_select's G x 4 wave slices, k_filter's block ranges for its grid)
         auto filt = k_filter<true>;
         s->csr_gsel = G;
-        s->csr_gfil = grid_for(TC, ARCS_PER_BLOCK,
-                               resident_grid((const void *)filt, BLOCK, s->seg_g, GHS_RESIDENT_GRIDS || !GHS_FILTER_CSR_W8));
+        s->csr_gfil = grid_for(TC, ARCS_PER_BLOCK, resident_grid((const void *)filt, BLOCK, s->seg_g));
         s->trow_ready = true;
         KT(GHS_K_CSR_TROW, s->n);
         uint32_t *rb = s->bsel + SEG_MAX + 1;  // (2 words past k_select's bounds)
@@ -4921,7 +4257,7 @@ static int open_level(ghs_solver *s, bool async_open = false) {
       // 1.62-1.63 ms), while k_select keeps the CSR stream (0.53 vs 0.68 ms)
       const bool fcsr = s->csr && !s->eu;
       auto filt = fcsr ? k_filter<true> : k_filter<false>;
-      G = fcsr ? s->csr_gfil : grid_for(TC, ARCS_PER_BLOCK, resident_grid((const void *)filt, BLOCK, s->seg_g));
+      G = fcsr ? s->csr_gfil : grid_for(TC, ARCS_PER_BLOCK, s->seg_g);
       if (TC) {
         GHS_HIP_CHECK(hipEventRecord(s->res->pass_ev[2], st));
         {
@@ -4947,7 +4283,7 @@ static int open_level(ghs_solver *s, bool async_open = false) {
     } else {
       // split the pending edges (total on the device): this level's inter-fragment edges -> Y;
       // heavier survivors -> RO regions. Fixed grid: block b owns 1/seg_g of the virtual range.
-      G = resident_grid((const void *)k_level_pass, BLOCK, s->lp_g);
+      G = s->lp_g;
       SegView in{RI.seg_start, RI.seg_prefix, s->rem_nseg};
       {
       KT(GHS_K_LEVEL_PASS, s->rem_total);
@@ -4977,21 +4313,18 @@ static int open_level(ghs_solver *s, bool async_open = false) {
 }
 
 // ---- dense levels (several ranks; kernels at k_dense_open) ------------------------------------
-#ifndef GHS_DENSE_PACK
-#define GHS_DENSE_PACK 1
-#endif
 static DenseRank dense_rank_of(const ghs_solver *s) {
   DenseRank r;
   r.bits = s->drank_bits;
   r.wpre = s->drank_wpre;
   r.cpre = s->drank_cpre;
-  r.pk = GHS_DENSE_PACK ? s->drank_pk : nullptr;
+  r.pk = s->drank_pk;
   return r;
 }
 
 // after k_rank_chunks: the packed table every dense_rank lookup of the level reads
 static void rank_pack(ghs_solver *s, uint64_t words) {
-  if (GHS_DENSE_PACK && s->drank_pk)
+  if (s->drank_pk)
     k_rank_pack<<<grid_for(words, 256, 8192), 256, 0, s->stream>>>(s->drank_bits, s->drank_wpre, s->drank_cpre, words,
                                                                   s->drank_pk);
 }
@@ -5156,35 +4489,15 @@ static void flush_scan(ghs_solver *s) {
 // ms vs 5.6 ms for the atomic min-edge + CONNECT); below the bound large fragments do the same
 // (the grid's level-0 rounds 4 and 5: 0.84 / 0.52 ms vs 0.55 / 0.17 ms), and the min-edge kernel's
 // LDS cache of fragment minima absorbs their candidates anyway.
-#ifndef GHS_BUCKET_MIN_ACTIVE
-#define GHS_BUCKET_MIN_ACTIVE (1u << 23)
-#endif
-constexpr uint64_t BUCKET_MIN_ACTIVE = GHS_BUCKET_MIN_ACTIVE;
-// a lattice-like solve also buckets the first round of every later level (the hot fragments
-// excluded). Off: on the 16384^2 grid level 0 stops at the bond-percolation point, so level 1 has
-// many large fragments below the hot list's size threshold, each filling one bucket (grid step
-// 43.6 -> 48.3 ms, gradient grid 18.8 -> 20.5 ms, same box; profiles/r03/hot2).
-#ifndef GHS_BK_LEVEL_FIRST
-#define GHS_BK_LEVEL_FIRST 0
-#endif
-constexpr bool BK_LEVEL_FIRST = GHS_BK_LEVEL_FIRST;
+constexpr uint64_t BUCKET_MIN_ACTIVE = 1u << 23;
+// (A lattice-like solve bucketing the first round of every later level too, and a random-like
+// graph's level 0 round 0 bucketed: DESIGN.md "Measured and rejected".)
 // k_jump_ident's grid cap on lattice-like solves. Path-splitting walks on long hook chains (the
 // gradient grid's columns) duplicate each other's work when too many start at once: the gradient
 // grid's level-0 jump took 1.8 ms at 2048 blocks and 3.6 ms at 16384; random graphs (short
 // chains) want every walk in flight (R-MAT s24 bucketed rounds: 0.46 ms at 2048 blocks, 0.34 at
 // 16384).
-#ifndef GHS_JUMP_LATTICE_G
-#define GHS_JUMP_LATTICE_G 2048
-#endif
-constexpr unsigned JUMP_LATTICE_G = GHS_JUMP_LATTICE_G;
-// a random-like graph's level 0 round 0 bucketed too (1) or by the a-run seeding + atomic min-edge +
-// k_win (0). Level 0 has no giant to reduce, so nearly every edge becomes two records in random
-// buckets, each a scattered 16-B store: R-MAT s26 round 0 2.56 ms bucketed vs 2.37 ms (s24 0.50
-// vs 0.52 ms), same box (profiles/r03/l0ab).
-#ifndef GHS_BK_RANDOM_L0
-#define GHS_BK_RANDOM_L0 0
-#endif
-constexpr bool BK_RANDOM_L0 = GHS_BK_RANDOM_L0;
+constexpr unsigned JUMP_LATTICE_G = 2048;
 
 // hot != nullptr (a level's first round past level 0: the hot list of k_giant): the hot fragments'
 // candidates are reduced by k_bucket into best[]; k_hot_hook then hooks them like k_bmin hooks a
@@ -5235,9 +4548,8 @@ static int enqueue_minedge(ghs_solver *s) {
   ArcBuf &O = s->buf[s->cur ^ 1];
   SegView in{I.seg_start, I.seg_prefix, s->cur_nseg};
   // GHS_OPT_BUCKETED (forced) runs every round bucketed: the test suite's coverage of them
-  s->round_bucketed = s->bucketed && (s->bucket_first_only ? (s->level_round == 0 && (BK_RANDOM_L0 || s->level > 0))
+  s->round_bucketed = s->bucketed && (s->bucket_first_only ? (s->level_round == 0 && s->level > 0)
                                       : ((s->level == 0 && s->nact >= BUCKET_MIN_ACTIVE) ||
-                                         (BK_LEVEL_FIRST && s->level > 0 && s->level_round == 0) ||
                                          (s->cfg.options & GHS_OPT_BUCKETED)));
   const bool windowed0 = s->level_round == 0 && (s->cur_arcs || !s->arcs_known) && s->round_bucketed &&
                          s->level == 0 && s->lattice && s->windowed;
@@ -5266,10 +4578,10 @@ static int enqueue_minedge(ghs_solver *s) {
           const unsigned wg = 8 * WM_CHUNK * ((s->bk_nb + 8 * WM_CHUNK - 1) / (8 * WM_CHUNK));
           if (s->bk_bs == 13)
             k_wmin<13><<<wg, BM_T, 0, s->stream>>>(I.src, I.dst, I.key, in, s->bk_nb, s->wstart, s->par, s->best,
-                                                  s->in_mst, far, s->n, WM_GATHER ? s->eu : nullptr, s->ev);
+                                                  s->in_mst, far, s->n, s->eu, s->ev);
           else
             k_wmin<14><<<wg, BM_T, 0, s->stream>>>(I.src, I.dst, I.key, in, s->bk_nb, s->wstart, s->par, s->best,
-                                                  s->in_mst, far, s->n, WM_GATHER ? s->eu : nullptr, s->ev);
+                                                  s->in_mst, far, s->n, s->eu, s->ev);
         }
         enqueue_bmin(s, I.src, I.dst, I.key, in, nullptr, items, nullptr, far, true);
       } else if (s->round_bucketed) {
@@ -5557,268 +4869,7 @@ static int decide_bucketed(ghs_solver *s) {
 }
 
 
-// ---- the LDS tail: the rest of a level once its active fragments fit LDS (one rank) ---------
-// Enters at a round >= 1 of a level whose exact active count is in [2, TAIL_MAX] (the host has
-// read every earlier report); enqueues batches of tail rounds (k_tail_round + k_tail_hook, no-ops
-// once the level is done) behind k_tail_map + k_tail_open, each batch ending with a copy of the
-// control block and its report; reads the tail's per-round stats from that copy and closes the
-// level. Rounds whose launches follow the finishing round exit at once.
-// Tail rounds per batch: the first batch is sized from the level's last observed contraction.
-// F0 fragments shrinking by `decay` per round leave <= 1 root after L = log_decay(F0) rounds of
-// hooks (the open's included), so k_tail_round r = ceil(L) is the finishing one and the batch holds
-// exactly the launches the level needs. The contraction slows inside a level (R-MAT s24 level 0:
-// 26x, 19x, 10x, 10x), so half a round of margin — none when the open's hooks alone are expected to
-// finish (F0 <= decay): R-MAT s24 levels 0 and 1 and both tails of the 16384^2 grid then launch no
-// round past the finishing one (profiles/r06/rounds_*.txt). An underestimate costs one more batch.
-constexpr uint32_t TAIL_BATCH_MIN = 1, TAIL_BATCH_MAX = 8;
-
-static uint32_t tail_first_batch(uint64_t F0, uint64_t prev_in) {
-  const double decay = std::max(2.0, prev_in > F0 ? (double)prev_in / (double)F0 : 2.0);
-  const double L = std::log((double)F0) / std::log(decay);
-  const double est = (double)F0 <= decay ? 1.0 : std::ceil(L + 0.5);
-  return (uint32_t)std::min<double>(TAIL_BATCH_MAX, std::max<double>(TAIL_BATCH_MIN, est));
-}
-constexpr uint64_t TAIL_TRY = 32ull * TAIL_MAX;  // a bound below this: read the exact count first
-
-static bool tail_usable(const ghs_solver *s) {
-  return s->tail_on && s->tail.ctl && s->cfg.num_ranks <= 1 && !s->level_dense && s->level_round >= 1 &&
-         !s->act_ident;
-}
-
-// map + labels + open (round 0's stream of the tail)
-static void tail_start(ghs_solver *s, TailRun &t, bool multi) {
-  hipStream_t st = s->stream;
-  ensure_lab(s);
-  t.tb = s->tail;
-  const ArcBuf &I = s->buf[s->cur], &O = s->buf[s->cur ^ 1];
-  t.tb.rec = O.src;  // the idle edge buffer holds the tail's records
-  t.tb.rkey = O.key;
-  if (s->scan_pending) flush_scan(s);
-  t.act0 = s->act[s->act_cur];
-  const unsigned long long *d_nact = cur_act_count(s);
-  SegView in{I.seg_start, I.seg_prefix, s->cur_nseg};
-  t.F0 = (uint32_t)s->nact;
-  t.hook_g = (t.F0 + TAIL_HS - 1) / TAIL_HS;
-  t.round0 = s->round;
-  t.lr0 = s->level_round;
-  t.r = 1;
-  t.multi = multi;
-  KT(GHS_K_TAIL_OPEN, s->arcs_known ? s->cur_arcs : 0);
-  k_tail_map<<<grid_for(t.F0, 256, 64), 256, 0, st>>>(t.act0, d_nact, t.tb);
-  // the labels the edges carry: the previous round's list (after the level's identity round 0:
-  // every vertex; a dense level's: every dense label)
-  const bool prev_ident = t.lr0 == 1;
-  const uint32_t *prev = prev_ident ? nullptr : s->act[s->act_cur ^ 1];
-  const unsigned long long *d_nprev =
-      prev_ident ? s->cnt + (s->level_dense ? C_NDENSE : C_N) : act_count(s, s->act_cur ^ 1);
-  const uint64_t nprev_bound = prev_ident ? (s->level_dense ? s->dense_n : s->n) : s->level_nact;
-  k_tail_labels<<<grid_for(nprev_bound, 256, 8192), 256, 0, st>>>(prev, d_nprev, s->lab, t.tb);
-  k_tail_open<<<TAIL_G, TAIL_T, 0, st>>>(I.src, I.dst, I.key, in, t.tb, s->check_totals);
-}
-
-// round rr's hooks: every root's minimum over the blocks' rows (several ranks: this rank's own,
-// agreed by tail_agree between the caller's two all-reduces)
-static int tail_hook_local(ghs_solver *s, const TailRun &t, uint32_t rr) {
-  s->round = t.round0 + rr;  // the profile's round index: the round whose stream they reduce
-  KT(GHS_K_TAIL_HOOK, rr ? 0 : t.F0);
-  k_tail_hook<<<t.hook_g, 256, 0, s->stream>>>(t.tb, rr, s->in_mst, TAIL_G, s->cnt + C_ERR, t.multi);
-  GHS_HIP_CHECK(hipGetLastError());
-  return GHS_OK;
-}
-
-static int tail_agree(ghs_solver *s, const TailRun &t, uint32_t rr) {
-  s->round = t.round0 + rr;
-  KT(GHS_K_TAIL_HOOK, 0);
-  k_tail_xhook<<<t.hook_g, 256, 0, s->stream>>>(t.tb, rr, s->in_mst, (uint32_t)s->e_lo, (uint32_t)s->e_hi);
-  GHS_HIP_CHECK(hipGetLastError());
-  return GHS_OK;
-}
-
-static int tail_round_launch(ghs_solver *s, const TailRun &t, uint32_t r) {
-  s->round = t.round0 + r;
-  KT(GHS_K_TAIL_ROUND, 0);
-  k_tail_round<<<TAIL_G, TAIL_T, 0, s->stream>>>(t.tb, r, t.act0, s->lab, s->cnt, s->cnt + C_ERR);
-  GHS_HIP_CHECK(hipGetLastError());
-  return GHS_OK;
-}
-
-// the control block (and the report, checksummed) behind the tail's launches so far: *nact_out = 0
-// once the level is done
-static int tail_report(ghs_solver *s, const TailRun &t, uint32_t last, unsigned long long *nact_out) {
-  hipStream_t st = s->stream;
-  const unsigned long long seq = ++s->res->seq;
-  RoundSlot *dslot = &s->d_slot[seq % SLOT_RING];
-  GHS_HIP_CHECK(hipMemcpyAsync(s->res->h_tail, t.tb.ctl, sizeof(TailCtl), hipMemcpyDeviceToHost, st));
-  k_tail_report<<<1, 1, 0, st>>>(t.tb, last, dslot, seq, s->cnt);
-  GHS_HIP_CHECK(hipGetLastError());
-  RoundSlot rep;
-  if (int rc = wait_slot(s, s->h_slot + (seq % SLOT_RING), seq, &rep)) return rc;
-  if (slot_err(rep.err)) return fail_counters(s, slot_err(rep.err), "in the LDS tail");
-  s->rep_weight = rep.weight;
-  s->rep_edges = rep.edges;
-  s->report_final = true;
-  if (s->debug)
-    fprintf(stderr, "[ghs] level %u tail report: nact_out %llu edges %llu weight %llu\n", s->level, rep.nact_out,
-            rep.edges, rep.weight);
-  *nact_out = rep.nact_out;
-  return GHS_OK;
-}
-
-// the level is done (the last report read): the tail rounds' stats, then the level's close
-static int tail_finish(ghs_solver *s, const TailRun &t) {
-  const TailCtl &c = *s->res->h_tail;
-  const uint32_t rounds = std::min(c.rounds, TAIL_ROUNDS_MAX);
-  for (uint32_t k = 0; k < rounds; ++k) push_stats(s, t.lr0 + k, c.live[k], c.nroots[k], c.edges[k]);
-  s->round = t.round0 + rounds;
-  s->level_round = t.lr0 + rounds;
-  s->tail_ran = true;
-  if (s->ev_rec.size() > s->round) s->ev_rec.resize(s->round);
-  if (int rc = check_level_totals(s)) return rc;
-  if (int rc = dense_close(s)) return rc;
-  close_level(s);
-  return GHS_OK;
-}
-
-// coll != nullptr: one rank of several (a dense level, ghs_solver_tail_multi) — each round's hooks
-// agree across the ranks through two small all-reduces (MIN of the F0 keys, MAX of the targets)
-static int run_tail(ghs_solver *s, uint64_t prev_in, const GhsTailColl *coll = nullptr) {
-  hipStream_t st = s->stream;
-  TailRun t;
-  tail_start(s, t, coll != nullptr);
-  auto hook = [&](uint32_t rr) -> int {
-    if (int rc = tail_hook_local(s, t, rr)) return rc;
-    if (coll) {
-      if (int rc = coll->min_u64(coll->ctx, t.tb.gkey, t.F0, st)) return rc;
-      if (int rc = tail_agree(s, t, rr)) return rc;
-      if (int rc = coll->max_i32(coll->ctx, reinterpret_cast<int32_t *>(t.tb.ghook), t.F0, st)) return rc;
-    }
-    return GHS_OK;
-  };
-  if (int rc = hook(0)) return rc;
-  uint32_t batch = tail_first_batch(t.F0, prev_in);
-  for (;;) {
-    const uint32_t last = std::min(t.r + batch - 1, TAIL_ROUNDS_MAX);  // the batch's last round
-    for (; t.r <= last; ++t.r) {
-      // round r - 1's hooks, unless the open's (launched above): a batch ends with a round, not with
-      // its hook kernel, so the round that finishes the level is not followed by a no-op hook launch
-      // when it closes its batch (the hook comes first in the next batch otherwise)
-      if (t.r > 1)
-        if (int rc = hook(t.r - 1)) return rc;
-      if (int rc = tail_round_launch(s, t, t.r)) return rc;
-    }
-    unsigned long long nact_out = 0;
-    if (int rc = tail_report(s, t, last, &nact_out)) return rc;
-    if (nact_out <= 1) break;
-    if (t.r > TAIL_ROUNDS_MAX) return fail_counters(s, 4, "in the LDS tail (round cap)");
-    // the next batch from the batch's last contraction (the report's copy of the control block:
-    // nroots[last] = nact_out roots entering round last's stream, nroots[last - 1] before them),
-    // sized like the first — R-MAT s26 level 0 (1189 -> 106 -> 14 -> 3 roots) then finishes in a
-    // batch of 1 instead of a fixed 3 with two no-op launch pairs
-    const TailCtl &c = *s->res->h_tail;
-    batch = tail_first_batch(nact_out, last >= 1 ? c.nroots[last - 1] : t.F0);
-  }
-  return tail_finish(s, t);
-}
-
-// The multi-rank loop's LDS tail (ghs_solver_run, multi.hip): at a round >= 1 of a dense level whose
-// active count is at most TAIL_MAX, the rounds still in flight are drained (their reports give the
-// exact count — every rank reads the same reports, so every rank takes the same branch), then the
-// level finishes in run_tail with the ranks' hooks agreed per round. Returns 0 when not applicable,
-// 1 when the level finished (in the drain or the tail), 2 when that ended the solve, or an error.
-int ghs_solver_tail_multi(ghs_solver *s, const GhsTailColl *coll) {
-  if (!s || !coll) return 0;
-  if (s->phase != 0 || !s->level_open || s->cfg.num_ranks <= 1 || !s->level_dense || !s->tail_on || !s->tail.ctl ||
-      s->act_ident || s->level_round < 1 || s->nact > TAIL_MAX)
-    return 0;
-  while (!s->pipe.empty()) {  // the rounds in flight (pipelined contract): their reports, in order
-    const ghs_solver::PipeRound p = s->pipe.front();
-    s->pipe.erase(s->pipe.begin());
-    RoundSlot rep;
-    if (int rc = wait_slot(s, s->h_slot + (p.seq % SLOT_RING), p.seq, &rep)) return rc;
-    if (slot_err(rep.err)) return fail_counters(s, slot_err(rep.err), ("in round " + std::to_string(p.round + 1)).c_str());
-    push_stats(s, p.level_round, s->pipe_live, rep.nact_in, rep.edges);
-    s->pipe_live = rep.live_out;
-    s->pipe_exact = rep.nact_out;
-    s->pipe_exact_lr = p.level_round + 1;
-    s->nact = rep.nact_out;
-    if (rep.nact_out <= 1) {  // the level ended with round p: the rounds enqueued after it are no-ops
-      s->pipe.clear();
-      s->round = p.round + 1;
-      s->level_round = p.level_round + 1;
-      if (int rc = dense_close(s)) return rc;
-      close_level(s);
-      return s->phase == 2 ? 2 : 1;
-    }
-  }
-  if (s->nact < 2) return 0;  // (the synchronous contract closes such a level itself)
-  if (int rc = run_tail(s, s->last_nact_in, coll)) return rc;
-  return s->phase == 2 ? 2 : 1;
-}
-
-static bool tail_step_usable(const ghs_solver *s) {
-  return s->phase == 0 && s->level_open && s->cfg.num_ranks > 1 && s->level_dense && s->tail_on && s->tail.ctl &&
-         !s->act_ident && s->level_round >= 1 && s->nact >= 2 && s->nact <= TAIL_MAX && s->pipe.empty();
-}
-
-extern "C" {
-
-// ---- the stepwise LDS tail (ABI 10; include/ghs_mst.h): the caller's collectives between the calls ----
-int ghs_solver_tail_begin(ghs_solver_t *s, uint64_t *num_fragments) {
-  if (!s || !num_fragments) GHS_FAIL(GHS_E_ARG, "solver/num_fragments is NULL");
-  *num_fragments = 0;
-  if (s->tail_step) GHS_FAIL(GHS_E_STATE, "a tail is already in progress");
-  if (!tail_step_usable(s)) return GHS_OK;
-  s->trun = TailRun();
-  tail_start(s, s->trun, true);
-  if (int rc = tail_hook_local(s, s->trun, 0)) return rc;
-  s->tail_step = true;
-  s->phase = 3;  // (minedge / contract refuse until the tail ends)
-  *num_fragments = s->trun.F0;
-  return GHS_OK;
-}
-
-int ghs_solver_tail_buffers(ghs_solver_t *s, uint64_t **d_keys, int32_t **d_hooks) {
-  if (!s || !d_keys || !d_hooks) GHS_FAIL(GHS_E_ARG, "solver/keys/hooks is NULL");
-  if (!s->tail_step) GHS_FAIL(GHS_E_STATE, "no tail in progress (ghs_solver_tail_begin)");
-  *d_keys = s->tail.gkey;
-  *d_hooks = reinterpret_cast<int32_t *>(s->tail.ghook);
-  return GHS_OK;
-}
-
-int ghs_solver_tail_agree(ghs_solver_t *s) {
-  if (!s) GHS_FAIL(GHS_E_ARG, "solver is NULL");
-  if (!s->tail_step) GHS_FAIL(GHS_E_STATE, "no tail in progress (ghs_solver_tail_begin)");
-  return tail_agree(s, s->trun, s->trun.r - 1);
-}
-
-int ghs_solver_tail_round(ghs_solver_t *s, int *state) {
-  if (!s || !state) GHS_FAIL(GHS_E_ARG, "solver/state is NULL");
-  *state = 0;
-  if (!s->tail_step) GHS_FAIL(GHS_E_STATE, "no tail in progress (ghs_solver_tail_begin)");
-  TailRun &t = s->trun;
-  if (t.r > TAIL_ROUNDS_MAX) {
-    s->tail_step = false;
-    return fail_counters(s, 4, "in the LDS tail (round cap)");
-  }
-  if (int rc = tail_round_launch(s, t, t.r)) return rc;
-  unsigned long long nact_out = 0;
-  if (int rc = tail_report(s, t, t.r, &nact_out)) {
-    s->tail_step = false;
-    return rc;
-  }
-  if (nact_out <= 1) {
-    s->tail_step = false;
-    s->phase = 0;
-    if (int rc = tail_finish(s, t)) return rc;
-    *state = s->phase == 2 ? 2 : 1;
-    return GHS_OK;
-  }
-  if (int rc = tail_hook_local(s, t, t.r)) return rc;
-  ++t.r;
-  return GHS_OK;
-}
-
-}  // extern "C"
+#include "boruvka/tail_driver.h"  // its host side: tail_*, run_tail, ghs_solver_tail_multi, ghs_solver_tail_* entry points
 
 
 static int run_level_pipelined(ghs_solver *s) {
@@ -6400,10 +5451,7 @@ int ghs_solver_contract_async(ghs_solver *s, int *done) {
     if (done) *done = 1;
     return GHS_OK;
   }
-#ifndef GHS_PIPE_MULTI
-#define GHS_PIPE_MULTI 1
-#endif
-  if (s->cfg.num_ranks <= 1 || s->level_round < 2 || !GHS_PIPE_MULTI) {
+  if (s->cfg.num_ranks <= 1 || s->level_round < 2) {
     const int rc = ghs_solver_contract(s, done);
     if (!rc && s->phase == 0 && s->level_round == 2) {  // round 2 comes next: its count is exact
       s->pipe.clear();

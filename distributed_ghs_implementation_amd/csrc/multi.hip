@@ -387,11 +387,9 @@ void comm_free(ghs_comm *c) {
 
 // the ranks' edge ranges balanced by the cost density 1 + RANGE_BETA * (1 - e / m) over the canonical
 // list — the closed form of device.py range_split / edge_range (see there), 4-aligned
-#ifndef GHS_RANGE_BETA
-#define GHS_RANGE_BETA 0.2
-#endif
+constexpr double RANGE_BETA = 0.2;
 uint64_t range_split(uint64_t m, int k, int N) {
-  const double b = GHS_RANGE_BETA;
+  const double b = RANGE_BETA;
   if (k <= 0) return 0;
   if (k >= N) return m;
   if (b == 0.0) return ((m * (uint64_t)k) / (uint64_t)N) & ~3ull;

@@ -1,15 +1,17 @@
 #!/bin/bash
 # Build libghs_mst.so from the working tree with extra compile flags into
 # distributed_ghs_implementation_amd/lib/exp/<name>.so (same-box A/B: tools/gpu/ab.sh with
-# GHS_MST_LIB=...). Usage: tools/build_variant.sh NAME "-DGHS_X=1 ..."
+# GHS_MST_LIB=...). The csrc Makefile does the build (its object list, its link line) into a
+# temporary OUTDIR; the shipped lib/ is untouched.
+# Usage: tools/build_variant.sh NAME "EXTRA_FLAGS"   e.g. tools/build_variant.sh o2 "-O2"
+#        (-DGHS_AB_ENV=1 gives the `make AB=1` build)
 set -e
 NAME=$1; EXTRA=$2
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 T=$(mktemp -d)
-cd "$ROOT/distributed_ghs_implementation_amd/csrc"
-F="-O3 -std=c++17 -fPIC --offload-arch=gfx950 $EXTRA"
-for s in boruvka ingest host multi; do /opt/rocm/bin/hipcc $F -c -o $T/$s.o $s.hip 2>&1 | grep -v hip-link || true; done
+trap 'rm -rf "$T"' EXIT
+make -C "$ROOT/distributed_ghs_implementation_amd/csrc" OUTDIR="$T" \
+  HIPFLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-result $EXTRA"
 mkdir -p "$ROOT/distributed_ghs_implementation_amd/lib/exp"
-/opt/rocm/bin/hipcc -shared --offload-arch=gfx950 -o "$ROOT/distributed_ghs_implementation_amd/lib/exp/$NAME.so" $T/boruvka.o $T/ingest.o $T/host.o $T/multi.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
-rm -rf "$T"
+mv "$T/libghs_mst.so" "$ROOT/distributed_ghs_implementation_amd/lib/exp/$NAME.so"
 echo "built $NAME.so with $EXTRA"
