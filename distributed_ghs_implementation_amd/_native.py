@@ -24,6 +24,11 @@ GHS_E_NODEVICE = -5
 GHS_E_NOMEM = -6
 GHS_E_STATE = -7
 GHS_MAX_ROUND_STATS = 64
+# ghs_weight_ranks_device's weight types (include/ghs_mst.h GHS_W_*)
+GHS_W_FLOAT32 = 0
+GHS_W_FLOAT64 = 1
+GHS_W_INT64 = 2
+GHS_W_UINT64 = 3
 
 _ERR_NAMES = {
     GHS_E_ARG: "GHS_E_ARG", GHS_E_NONCANON: "GHS_E_NONCANON", GHS_E_HIP: "GHS_E_HIP",
@@ -50,6 +55,7 @@ EXPORTED_SYMBOLS = (
     "ghs_mst_device_csr", "ghs_csr_offsets", "ghs_solver_create_csr",
     "ghs_batch_workspace_bytes", "ghs_mst_batch_device", "ghs_mst_batch_host",
     "ghs_canonicalize_temp_bytes", "ghs_canonicalize_device",
+    "ghs_weight_ranks_temp_bytes", "ghs_weight_ranks_device",
 )
 
 
@@ -323,6 +329,9 @@ def load():
             # ABI 10 addition: device ingest (raw edge list -> canonical list + raw indices)
             "ghs_canonicalize_temp_bytes": (sz, [u32, u64]),
             "ghs_canonicalize_device": (i32, [u32, u64, vp, vp, vp, vp, vp, vp, vp, P(u64), vp, sz, vp]),
+            # ABI 10 addition: float / 64-bit weights -> dense ranks (the uint32 engine weights)
+            "ghs_weight_ranks_temp_bytes": (sz, [u32, u64]),
+            "ghs_weight_ranks_device": (i32, [u32, u64, vp, vp, P(u64), vp, sz, vp]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(L, name)

@@ -7,7 +7,9 @@
 // canonical sort/dedupe is a rocPRIM radix sort of 64-bit (min << scale | max) keys, then a
 // two-pass unique + decode (k_uniq_*). ghs_canonicalize_device is the general form of that stage for
 // a caller's raw edge list (k_canon_*: the nx.Graph construction every reference entry point starts
-// with, ghs_implementation.py:425-426, on the device).
+// with, ghs_implementation.py:425-426, on the device). ghs_weight_ranks_device (k_weight_keys,
+// k_rank_*) comes in front of it for float / 64-bit weights: nx.Graph takes any comparable weight,
+// the engine uint32, and the dense rank among the distinct values is an order- and tie-preserving map.
 // The CPU restatement of both generators (test infrastructure) is oracle/generators.c.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -352,6 +354,196 @@ static inline uint32_t canon_bits(uint32_t n) {
   return bits;
 }
 
+// ---- weight ranks (ABI 10 addition, ghs_weight_ranks_device) ---------------------------------
+// The device form of graph._as_weight_array's np.searchsorted(np.unique(w), w): the solver's key is
+// (w, eid), so any order-preserving map of the weights that keeps ties tied gives the same flags,
+// and float / 64-bit weights reach the uint32 engine as their dense rank among the distinct values.
+// Pass 1 (k_weight_keys) maps every weight to an unsigned key that orders as the value does, with the
+// element's index as the sort's value; a pairs sort (no stability needed: equal keys get equal
+// ranks); then head flags over the sorted keys (a key that differs from its predecessor opens a new
+// rank) in the tile shape of the compaction above — but here EVERY element writes: its rank is the
+// number of heads up to and including it, minus one, scattered to ranks[index].
+template <uint32_t WT>
+struct WeightKey;
+template <>
+struct WeightKey<GHS_W_FLOAT32> {
+  typedef uint32_t key_t;
+  static __device__ __forceinline__ key_t key(key_t b, bool *nan) {
+    const key_t sign = 0x80000000u, mag = b & ~sign;
+    if (mag > 0x7f800000u) *nan = true;
+    if (mag == 0) b = 0;  // -0.0 == +0.0
+    return (b & sign) ? ~b : (b | sign);
+  }
+};
+template <>
+struct WeightKey<GHS_W_FLOAT64> {
+  typedef uint64_t key_t;
+  static __device__ __forceinline__ key_t key(key_t b, bool *nan) {
+    const key_t sign = 1ull << 63, mag = b & ~sign;
+    if (mag > 0x7ff0000000000000ull) *nan = true;
+    if (mag == 0) b = 0;
+    return (b & sign) ? ~b : (b | sign);
+  }
+};
+template <>
+struct WeightKey<GHS_W_INT64> {
+  typedef uint64_t key_t;
+  static __device__ __forceinline__ key_t key(key_t b, bool *) { return b ^ (1ull << 63); }
+};
+template <>
+struct WeightKey<GHS_W_UINT64> {
+  typedef uint64_t key_t;
+  static __device__ __forceinline__ key_t key(key_t b, bool *) { return b; }
+};
+
+// Elements [head, head + VEC * nvec) are read as 16-byte vectors (VEC = 4 or 2 elements; the host
+// picks head so that w + head is 16-byte aligned), the other nscalar elements one by one. keys /
+// vals are 256-byte aligned, so with head = 0 the key stores are 16-byte vectors too.
+template <uint32_t WT>
+__global__ __launch_bounds__(BLOCK) void k_weight_keys(uint64_t head, uint64_t nvec, uint64_t nscalar,
+                                                       const typename WeightKey<WT>::key_t *__restrict__ w,
+                                                       typename WeightKey<WT>::key_t *__restrict__ keys,
+                                                       uint32_t *__restrict__ vals, unsigned int *__restrict__ err) {
+  typedef typename WeightKey<WT>::key_t K;
+  constexpr int VEC = 16 / sizeof(K);
+  typedef K kvec __attribute__((ext_vector_type(VEC)));
+  typedef uint32_t ivec __attribute__((ext_vector_type(VEC)));
+  const uint64_t gid = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  bool nan = false;
+  for (uint64_t q = gid; q < nvec; q += stride) {
+    const uint64_t i = head + VEC * q;
+    const kvec b = *reinterpret_cast<const kvec *>(w + i);
+    kvec k;
+#pragma unroll
+    for (int x = 0; x < VEC; ++x) k[x] = WeightKey<WT>::key(b[x], &nan);
+    ivec iv;
+#pragma unroll
+    for (int x = 0; x < VEC; ++x) iv[x] = (uint32_t)(i + x);
+    if (head == 0) {
+      *reinterpret_cast<kvec *>(keys + i) = k;
+      *reinterpret_cast<ivec *>(vals + i) = iv;
+    } else {
+#pragma unroll
+      for (int x = 0; x < VEC; ++x) {
+        keys[i + x] = k[x];
+        vals[i + x] = iv[x];
+      }
+    }
+  }
+  for (uint64_t s = gid; s < nscalar; s += stride) {
+    const uint64_t i = s < head ? s : VEC * nvec + s;
+    keys[i] = WeightKey<WT>::key(w[i], &nan);
+    vals[i] = (uint32_t)i;
+  }
+  if (nan) atomicOr(err, 1u);
+}
+
+// a sorted entry opens a new rank when it is the first or differs from its predecessor (read across
+// lane, wave, block and tile boundaries alike: it is the previous array element)
+template <typename K>
+__device__ __forceinline__ bool wr_head(const K *__restrict__ keys, uint64_t i, uint64_t T) {
+  if (i >= T) return false;
+  return i == 0 || keys[i - 1] != keys[i];
+}
+
+template <typename K>
+__global__ __launch_bounds__(UQ_BLOCK) void k_rank_count(const K *__restrict__ keys, uint64_t T,
+                                                         uint32_t *__restrict__ tile_cnt) {
+  __shared__ uint32_t s_w[UQ_BLOCK / 64];
+  const uint64_t base = blockIdx.x * UQ_TILE;
+  uint32_t c = 0;
+#pragma unroll
+  for (int j = 0; j < UQ_ROWS; ++j) c += wr_head(keys, base + (uint64_t)j * UQ_BLOCK + threadIdx.x, T) ? 1u : 0u;
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d);
+  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x / 64] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t t = 0;
+    for (int w = 0; w < UQ_BLOCK / 64; ++w) t += s_w[w];
+    tile_cnt[blockIdx.x] = t;
+  }
+}
+
+// every element, to ranks[its index]: (heads before the tile) + (heads of the tile up to and
+// including it) - 1. The first element of the array is a head, so the sum is >= 1 everywhere; the
+// in-tile prefix runs on across the tile's rows (row_base), unlike a compaction's per-survivor slot.
+template <typename K>
+__global__ __launch_bounds__(UQ_BLOCK) void k_rank_write(const K *__restrict__ keys, const uint32_t *__restrict__ vals,
+                                                         uint64_t T, const uint32_t *__restrict__ tile_off,
+                                                         uint32_t *__restrict__ ranks) {
+  __shared__ uint32_t s_cnt[UQ_ROWS][UQ_BLOCK / 64];
+  const uint64_t base = blockIdx.x * UQ_TILE;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x / 64;
+  const uint64_t le = ((1ull << lane) - 1ull) | (1ull << lane);
+  uint64_t masks[UQ_ROWS];
+#pragma unroll
+  for (int j = 0; j < UQ_ROWS; ++j) {
+    masks[j] = __ballot(wr_head(keys, base + (uint64_t)j * UQ_BLOCK + threadIdx.x, T));
+    if (lane == 0) s_cnt[j][wid] = (uint32_t)__popcll(masks[j]);
+  }
+  __syncthreads();
+  uint32_t row_base = tile_off[blockIdx.x];
+#pragma unroll
+  for (int j = 0; j < UQ_ROWS; ++j) {
+    uint32_t before = 0, row = 0;
+#pragma unroll
+    for (int x = 0; x < UQ_BLOCK / 64; ++x) {
+      const uint32_t c = s_cnt[j][x];
+      before += x < wid ? c : 0u;
+      row += c;
+    }
+    const uint64_t i = base + (uint64_t)j * UQ_BLOCK + threadIdx.x;
+    if (i < T) ranks[vals[i]] = row_base + before + (uint32_t)__popcll(masks[j] & le) - 1u;
+    row_base += row;
+  }
+}
+
+static inline size_t weight_key_bytes(uint32_t wtype) { return wtype == GHS_W_FLOAT32 ? 4 : 8; }
+
+static size_t weight_prim_bytes(uint32_t wtype, uint64_t m) {
+  size_t sort_b = 0;
+  if (wtype == GHS_W_FLOAT32)
+    (void)rocprim::radix_sort_pairs(nullptr, sort_b, (const uint32_t *)nullptr, (uint32_t *)nullptr,
+                                    (const uint32_t *)nullptr, (uint32_t *)nullptr, (size_t)m, 0u, 32u);
+  else
+    (void)rocprim::radix_sort_pairs(nullptr, sort_b, (const uint64_t *)nullptr, (uint64_t *)nullptr,
+                                    (const uint32_t *)nullptr, (uint32_t *)nullptr, (size_t)m, 0u, 64u);
+  const size_t tiles_b = ((m + UQ_TILE - 1) / UQ_TILE) * 4;
+  return align256(sort_b > tiles_b ? sort_b : tiles_b);
+}
+
+// the enqueue of ghs_weight_ranks_device for one weight type: status[0] = distinct, [1] = NaN flag
+template <uint32_t WT>
+static int weight_ranks_enqueue(uint64_t T, const void *d_weights, uint32_t *d_ranks, char *base, uint64_t *status,
+                                void *prim_temp, size_t prim_bytes, hipStream_t st) {
+  typedef typename WeightKey<WT>::key_t K;
+  constexpr uint64_t VEC = 16 / sizeof(K);
+  const size_t ak = align256(T * sizeof(K)), a4 = align256(T * 4);
+  K *ka = (K *)base;
+  K *kb = (K *)(base + ak);
+  uint32_t *va = (uint32_t *)(base + 2 * ak);
+  uint32_t *vb = (uint32_t *)(base + 2 * ak + a4);
+  const uint64_t ntiles = (T + UQ_TILE - 1) / UQ_TILE;
+  uint32_t *tiles = (uint32_t *)prim_temp;  // reused after the sort
+  uint64_t head = ((16 - ((uintptr_t)d_weights & 15)) & 15) / sizeof(K);
+  if (head > T) head = T;
+  const uint64_t nvec = (T - head) / VEC, nscalar = T - VEC * nvec;
+
+  GHS_HIP_CHECK(hipMemsetAsync(status, 0, 16, st));
+  k_weight_keys<WT><<<grid_cap(nvec > nscalar ? nvec : nscalar, BLOCK, 2048), BLOCK, 0, st>>>(
+      head, nvec, nscalar, (const K *)d_weights, ka, va, (unsigned int *)(status + 1));
+  GHS_HIP_CHECK(hipGetLastError());
+  GHS_HIP_CHECK(rocprim::radix_sort_pairs(prim_temp, prim_bytes, ka, kb, va, vb, (size_t)T, 0u,
+                                          (unsigned int)(8 * sizeof(K)), st));
+  k_rank_count<K><<<(unsigned)ntiles, UQ_BLOCK, 0, st>>>(kb, T, tiles);
+  k_uniq_scan<<<1, 1024, 0, st>>>(tiles, (uint32_t)ntiles, status);
+  k_rank_write<K><<<(unsigned)ntiles, UQ_BLOCK, 0, st>>>(kb, vb, T, tiles, d_ranks);
+  GHS_HIP_CHECK(hipGetLastError());
+  return GHS_OK;
+}
+
 // ---- grid ----------------------------------------------------------------------------------
 __global__ void k_grid(uint32_t k, uint32_t mode, uint64_t wseed, uint32_t *__restrict__ u, uint32_t *__restrict__ v,
                        uint32_t *__restrict__ w) {
@@ -521,6 +713,65 @@ int ghs_canonicalize_device(uint32_t n, uint64_t m_raw, const uint32_t *d_ru, co
     GHS_FAIL(GHS_E_ARG, "vertex id out of range: a raw endpoint is >= n = " + std::to_string(n));
   if (h_status[0] >= (1ull << 31)) GHS_FAIL(GHS_E_ARG, "the canonical edge count must be < 2^31");
   *m_out = h_status[0];
+  return GHS_OK;
+}
+
+// temp layout: keys in / out (4 or 8 B per weight each), indices in / out (4 B each), a 256-byte
+// status block (distinct count, NaN flag), then rocPRIM's sort storage, reused for the tile counts
+size_t ghs_weight_ranks_temp_bytes(uint32_t wtype, uint64_t m) {
+  if (wtype > GHS_W_UINT64 || m == 0 || m >= (1ull << 32)) return 0;
+  return 2 * align256(m * weight_key_bytes(wtype)) + 2 * align256(m * 4) + 256 + weight_prim_bytes(wtype, m);
+}
+
+int ghs_weight_ranks_device(uint32_t wtype, uint64_t m, const void *d_weights, uint32_t *d_ranks, uint64_t *distinct,
+                            void *d_temp, size_t temp_bytes, void *stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (wtype > GHS_W_UINT64) GHS_FAIL(GHS_E_ARG, "unknown weight type " + std::to_string(wtype));
+  if (!distinct) GHS_FAIL(GHS_E_ARG, "distinct is NULL");
+  *distinct = 0;
+  if (m == 0) return GHS_OK;
+  if (m >= (1ull << 32)) GHS_FAIL(GHS_E_ARG, "m must be < 2^32");
+  if (!d_weights || !d_ranks || !d_temp) GHS_FAIL(GHS_E_ARG, "NULL pointer");
+  const size_t kb = weight_key_bytes(wtype);
+  if ((uintptr_t)d_weights & (kb - 1))
+    GHS_FAIL(GHS_E_ARG, "weights must be aligned to their element size (" + std::to_string(kb) + " bytes)");
+  if ((uintptr_t)d_ranks & 3) GHS_FAIL(GHS_E_ARG, "ranks must be 4-byte aligned");
+  if ((uintptr_t)d_temp & 15) GHS_FAIL(GHS_E_ARG, "temp must be 16-byte aligned");
+  const size_t need = ghs_weight_ranks_temp_bytes(wtype, m);
+  if (temp_bytes < need) GHS_FAIL(GHS_E_NOMEM, "temp too small");
+  const uintptr_t r0 = (uintptr_t)d_ranks, r1 = r0 + m * 4;
+  if ((r0 < (uintptr_t)d_weights + m * kb && (uintptr_t)d_weights < r1) ||
+      (r0 < (uintptr_t)d_temp + need && (uintptr_t)d_temp < r1))
+    GHS_FAIL(GHS_E_ARG, "ranks must not overlap the weights or temp");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) GHS_FAIL(GHS_E_NODEVICE, "no HIP device");
+
+  const size_t ak = align256(m * kb), a4 = align256(m * 4);
+  char *base = (char *)d_temp;
+  uint64_t *status = (uint64_t *)(base + 2 * ak + 2 * a4);  // [0] distinct count, [1] NaN flag
+  void *prim_temp = base + 2 * ak + 2 * a4 + 256;
+  const size_t prim_bytes = weight_prim_bytes(wtype, m);
+  int rc = GHS_OK;
+  switch (wtype) {
+    case GHS_W_FLOAT32:
+      rc = weight_ranks_enqueue<GHS_W_FLOAT32>(m, d_weights, d_ranks, base, status, prim_temp, prim_bytes, st);
+      break;
+    case GHS_W_FLOAT64:
+      rc = weight_ranks_enqueue<GHS_W_FLOAT64>(m, d_weights, d_ranks, base, status, prim_temp, prim_bytes, st);
+      break;
+    case GHS_W_INT64:
+      rc = weight_ranks_enqueue<GHS_W_INT64>(m, d_weights, d_ranks, base, status, prim_temp, prim_bytes, st);
+      break;
+    default:
+      rc = weight_ranks_enqueue<GHS_W_UINT64>(m, d_weights, d_ranks, base, status, prim_temp, prim_bytes, st);
+      break;
+  }
+  if (rc != GHS_OK) return rc;
+  uint64_t h_status[2] = {0, 0};
+  GHS_HIP_CHECK(hipMemcpyAsync(h_status, status, 16, hipMemcpyDeviceToHost, st));
+  GHS_HIP_CHECK(hipStreamSynchronize(st));
+  if (h_status[1]) GHS_FAIL(GHS_E_ARG, "NaN weight: weights must be comparable numbers");
+  *distinct = h_status[0];
   return GHS_OK;
 }
 

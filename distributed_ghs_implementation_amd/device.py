@@ -29,13 +29,17 @@ class DeviceEdges:
     (ABI 9, optional): the CSR row offsets of the same list (n + 1 entries, `with_csr()`); an
     engine built with csr=True streams (off, v, w) — 8 B per edge instead of 12 — and u may then
     be dropped (`csr_only()`). `src` (optional, lists made by `canonicalize_device` / `from_raw`):
-    per canonical edge, the index of the caller's raw edge it came from (int32, uint32 bits)."""
+    per canonical edge, the index of the caller's raw edge it came from (int32, uint32 bits).
+    `weights` (optional, lists made with rank_weights=True): the caller's own weights in canonical
+    order (w_raw[src], on the device) when w holds their ranks; `to_host()` hands them on as
+    `CanonicalGraph.weights`, so results report the caller's values."""
 
-    def __init__(self, n, u, v, w, off=None, src=None):
+    def __init__(self, n, u, v, w, off=None, src=None, weights=None):
         self.n = int(n)
         self.u, self.v, self.w = u, v, w
         self.off = off
         self.src = src
+        self.weights = weights
 
     @property
     def m(self):
@@ -53,7 +57,7 @@ class DeviceEdges:
     def csr_only(self):
         """The CSR form alone (u released): off, v, w."""
         self.with_csr()
-        return DeviceEdges(self.n, None, self.v, self.w, self.off, self.src)
+        return DeviceEdges(self.n, None, self.v, self.w, self.off, self.src, self.weights)
 
     @property
     def device(self):
@@ -67,15 +71,31 @@ class DeviceEdges:
         return cls(graph.n, dev(graph.u), dev(graph.v), dev(graph.w))
 
     @classmethod
-    def from_raw(cls, n, u, v, w, device="cuda"):
+    def from_raw(cls, n, u, v, w, device="cuda", rank_weights=False):
         """Raw numpy integer arrays (any order, either orientation, repeats, self-loops) -> the
         canonical list, sorted and de-duplicated on the device (`canonicalize_device`): one H2D copy
-        of the three arrays, no host sort. Values outside [0, 2^32) raise ValueError."""
-        packed = _pack_raw(u, v, w)
+        of the three arrays, no host sort. Values outside [0, 2^32) raise ValueError.
+        rank_weights=True: w may be any float or integer array (float16 is widened to float32,
+        integers narrower than 64 bits to int64; uint64 is accepted); it travels in its own H2D copy
+        at full width and is rank-mapped on the device (`weight_ranks`), and the result's `weights`
+        holds the caller's values. A NaN raises GHSError (GHS_E_ARG)."""
+        if not rank_weights:
+            packed = _pack_raw(u, v, w)
+            _native.load()
+            _native.require_gpu()
+            dev = torch.from_numpy(packed.view("int32")).to(device)
+            return canonicalize_device(n, dev[0], dev[1], dev[2])
+        import numpy as np
+        wa = np.asarray(w)
+        if wa.ndim != 1:
+            raise ValueError("u, v, w must be one-dimensional arrays of equal length")
+        packed = _pack_u32((("u", u), ("v", v)), len(wa))
+        wa, wtype = _rankable_array(wa)
         _native.load()
         _native.require_gpu()
         dev = torch.from_numpy(packed.view("int32")).to(device)
-        return canonicalize_device(n, dev[0], dev[1], dev[2])
+        wt = torch.from_numpy(np.ascontiguousarray(wa)).to(device)
+        return _canonicalize_ranked(n, dev[0], dev[1], wt, wtype)
 
     def raw_eids(self, in_mst):
         """The caller's edge indices of the MSF edges (in_mst: the m flags of a solve of this list),
@@ -95,20 +115,29 @@ class DeviceEdges:
 
     def to_host(self):
         from .graph import CanonicalGraph
+        weights = None if self.weights is None else self.weights.cpu().numpy()
         return CanonicalGraph(self.n, self.u_host(), self.v.cpu().numpy().view("uint32"),
-                              self.w.cpu().numpy().view("uint32"))
+                              self.w.cpu().numpy().view("uint32"), weights=weights)
 
 
 def _pack_raw(u, v, w):
     """Raw numpy integer arrays -> one (3, m) uint32 array (a single H2D copy); ValueError for
     anything but integers in [0, 2^32)."""
+    return _pack_u32((("u", u), ("v", v), ("w", w)))
+
+
+def _pack_u32(named, m=None):
+    """[(name, array)] -> one (k, m) uint32 array; m: the length every array must have (default:
+    the first one's)."""
     import numpy as np
-    arrs = [np.asarray(a) for a in (u, v, w)]
-    m = len(arrs[0]) if arrs[0].ndim == 1 else -1
+    names = [name for name, _ in named]
+    arrs = [np.asarray(a) for _, a in named]
+    if m is None:
+        m = len(arrs[0]) if arrs[0].ndim == 1 else -1
     if any(a.ndim != 1 or len(a) != m for a in arrs):
         raise ValueError("u, v, w must be one-dimensional arrays of equal length")
-    packed = np.empty((3, m), dtype=np.uint32)
-    for k, (name, a) in enumerate(zip(("u", "v", "w"), arrs)):
+    packed = np.empty((len(arrs), m), dtype=np.uint32)
+    for k, (name, a) in enumerate(zip(names, arrs)):
         if a.size == 0:
             continue
         if a.dtype.kind not in "iu":
@@ -133,19 +162,113 @@ def _as_u32_tensor(t, name):
     return torch.where(t >= (1 << 31), t - (1 << 32), t).to(torch.int32)
 
 
-def canonicalize_device(n, u, v, w, keep_src=True):
+def _rankable_array(w):
+    """A numpy weight array -> (array of a dtype ghs_weight_ranks_device takes, its GHS_W_* code):
+    float32 / float64 / int64 / uint64 as they are, float16 widened to float32, bool and narrower
+    integers to int64 (both exact). Anything else (strings, complex, objects): ValueError."""
+    import numpy as np
+    if w.dtype == np.float32:
+        return w, _native.GHS_W_FLOAT32
+    if w.dtype == np.float64:
+        return w, _native.GHS_W_FLOAT64
+    if w.dtype == np.float16:
+        return w.astype(np.float32), _native.GHS_W_FLOAT32
+    if w.dtype == np.uint64:
+        return w.view(np.int64), _native.GHS_W_UINT64  # torch moves it as int64 bits
+    if w.dtype.kind in "iub":
+        return w.astype(np.int64, copy=False), _native.GHS_W_INT64
+    raise ValueError(f"w: rank_weights takes float16 / float32 / float64 or integer weights, got {w.dtype}")
+
+
+_W_TYPES = {torch.float32: _native.GHS_W_FLOAT32, torch.float64: _native.GHS_W_FLOAT64,
+            torch.int64: _native.GHS_W_INT64}
+_W_WIDEN = {torch.float16: torch.float32, torch.bfloat16: torch.float32, torch.bool: torch.int64,
+            torch.uint8: torch.int64, torch.int8: torch.int64, torch.int16: torch.int64, torch.int32: torch.int64}
+
+
+def weight_ranks(w, wtype=None):
+    """Dense ranks of a weight tensor, on the device (ghs_weight_ranks_device: key pass, rocPRIM
+    pairs sort, head-flag scan + scatter): w is a one-dimensional GPU tensor of float32, float64 or
+    int64; returns (ranks, distinct) with ranks an int32 tensor of uint32 bit patterns equal to
+    np.searchsorted(np.unique(w), w) (-0.0 == +0.0, +-inf ordinary, denormals distinct, float64 never
+    narrowed) and distinct the number of distinct values. wtype: the GHS_W_* code when it is not the
+    dtype's own — _native.GHS_W_UINT64 for an int64 tensor holding uint64 bit patterns. Runs on
+    torch's current stream; a NaN raises GHSError (GHS_E_ARG)."""
+    if not (isinstance(w, torch.Tensor) and w.dim() == 1):
+        raise ValueError("w: a one-dimensional GPU tensor expected")
+    if hasattr(torch, "uint64") and w.dtype == torch.uint64:
+        w, wtype = w.view(torch.int64), _native.GHS_W_UINT64
+    if w.dtype not in _W_TYPES:
+        raise ValueError(f"w: float32, float64 or int64 tensor expected, got {w.dtype}")
+    if wtype is None:
+        wtype = _W_TYPES[w.dtype]
+    elif wtype != _W_TYPES[w.dtype] and not (wtype == _native.GHS_W_UINT64 and w.dtype == torch.int64):
+        raise ValueError(f"w: weight type {wtype} does not fit a {w.dtype} tensor")
+    L = _native.load()
+    _native.require_gpu()
+    if not w.is_cuda:
+        raise ValueError("w: a one-dimensional GPU tensor expected")
+    if w.numel() and w.stride(0) != 1:
+        w = w.contiguous()  # a slice stays a view: only its element's own alignment is needed
+    m, dev = int(w.numel()), w.device
+    if m >= (1 << 32):
+        raise ValueError("at most 2^32 - 1 weights")
+    with torch.cuda.device(dev):
+        ranks = torch.empty(m, dtype=torch.int32, device=dev)
+        tb = int(L.ghs_weight_ranks_temp_bytes(wtype, m))
+        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=dev)
+        distinct = ctypes.c_uint64(0)
+        _native.check(L.ghs_weight_ranks_device(wtype, m, _ptr(w), _ptr(ranks), ctypes.byref(distinct), _ptr(tmp), tb,
+                                                _stream()))
+    del tmp
+    return ranks, distinct.value
+
+
+def _canonicalize_ranked(n, u, v, w, wtype=None):
+    """canonicalize_device's rank_weights=True path: w (float32 / float64 / int64 GPU tensor; wtype
+    as weight_ranks takes it) -> ranks -> the canonicalisation with the raw indices kept -> the
+    caller's values gathered into canonical order."""
+    for name, t in (("u", u), ("v", v), ("w", w)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 1):
+            raise ValueError(f"{name}: a one-dimensional GPU tensor expected (DeviceEdges.from_raw takes numpy arrays)")
+    if not (u.numel() == v.numel() == w.numel()):
+        raise ValueError("u, v, w must have equal length")
+    if not (u.device == v.device == w.device):
+        raise ValueError("u, v, w must be on one device")
+    if hasattr(torch, "uint64") and w.dtype == torch.uint64:
+        w, wtype = w.view(torch.int64), _native.GHS_W_UINT64
+    ranks, _ = weight_ranks(w, wtype)
+    e = canonicalize_device(n, u, v, ranks, keep_src=True)
+    # raw indices below 2^31 index as the int32 they are (no widening pass over src)
+    weights = w[e.src if w.numel() <= (1 << 31) else e.src.to(torch.int64) & 0xFFFFFFFF]
+    if wtype == _native.GHS_W_UINT64:
+        weights = weights.view(torch.uint64)
+    e.weights = weights
+    return e
+
+
+def canonicalize_device(n, u, v, w, keep_src=True, rank_weights=False):
     """Raw edges in HBM -> canonical DeviceEdges, without leaving the device
     (ghs_canonicalize_device: key pass, stable pairs sort, last-of-run compaction). u, v, w: torch
     tensors on the GPU, int32 (uint32 bit patterns) or int64 (range-checked, ValueError outside
     [0, 2^32)); any vertex order, either orientation, repeats and self-loops allowed, with
     nx.Graph semantics (self-loops dropped, the LAST weight given for a pair wins). keep_src: the
     result's `src` holds, per canonical edge, the index of the raw edge it came from (`raw_eids`).
-    Runs on torch's current stream; a vertex id >= n raises GHSError (GHS_E_ARG)."""
+    Runs on torch's current stream; a vertex id >= n raises GHSError (GHS_E_ARG).
+    rank_weights=True: w may be a float (float16 / bfloat16 widened to float32, float32, float64)
+    or any integer tensor holding any values (widened to int64; torch.uint64 accepted): the engine
+    weights are their dense ranks (`weight_ranks`: order kept, ties kept, so the same MSF as the
+    host path's rank map), keep_src is forced on, and the result's `weights` holds the caller's
+    values in canonical order. A NaN raises GHSError (GHS_E_ARG)."""
     n = int(n)
     if n < 0 or n >= (1 << 32):
         raise ValueError("n must be in [0, 2^32)")
     L = _native.load()
     _native.require_gpu()
+    if rank_weights:
+        if isinstance(w, torch.Tensor) and w.dtype in _W_WIDEN:
+            w = w.to(_W_WIDEN[w.dtype])
+        return _canonicalize_ranked(n, u, v, w)
     for name, t in (("u", u), ("v", v), ("w", w)):
         if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 1):
             raise ValueError(f"{name}: a one-dimensional GPU tensor expected (DeviceEdges.from_raw takes numpy arrays)")

@@ -86,19 +86,22 @@ def minimum_spanning_forest(graph, num_gpus=1, devices=None, config=None):
     return out
 
 
-def minimum_spanning_forest_edges(num_nodes, u, v, w):
+def minimum_spanning_forest_edges(num_nodes, u, v, w, rank_weights=False):
     """Raw edge arrays -> MSTResult, canonicalized on the device: u, v, w are integer arrays in any
     order, either orientation, with repeats and self-loops (nx.Graph semantics: the last weight
     given for a pair wins), weights in [0, 2^32). One H2D copy, the sort / de-duplication and the
     solve on the GPU (DeviceEdges.from_raw -> DeviceMST.run), then the canonical list comes back for
     edges() / triples() / to_dict(). `raw_ids` of the result: for every MSF edge, the index of the
     caller's edge it is. Other weights (negative, float, larger) raise ValueError: `canonicalize`
-    rank-maps them on the host."""
+    rank-maps them on the host — or, with rank_weights=True, the device does (any float or integer
+    array; `device.weight_ranks`), and the result reports the caller's values exactly as
+    minimum_spanning_forest(canonicalize(...)) does. A NaN then raises GHSError (GHS_E_ARG)."""
     from .device import DeviceEdges, DeviceMST
     n = int(num_nodes)
     if n < 0 or n >= (1 << 32):
         raise ValueError("num_nodes must be in [0, 2^32)")
-    edges = DeviceEdges.from_raw(n, u, v, w)  # ValueError (bad values) before anything touches the device
+    # ValueError (bad values) before anything touches the device
+    edges = DeviceEdges.from_raw(n, u, v, w, rank_weights=rank_weights)
     eng = DeviceMST(edges)
     res, stats = eng.run()
     graph = edges.to_host()

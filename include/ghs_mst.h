@@ -295,6 +295,35 @@ int ghs_canonicalize_device(uint32_t n, uint64_t m_raw,
                             uint32_t *d_u, uint32_t *d_v, uint32_t *d_w, uint32_t *d_src /* may be NULL */,
                             uint64_t *m_out, void *d_temp, size_t temp_bytes, void *stream);
 
+/* ---- weight ranks: float / 64-bit weights -> uint32 engine weights (ABI 10 addition) --------
+ * The reference accepts any comparable weight (nx.Graph, ghs_implementation.py:417-440); the engine
+ * computes on uint32. Its key is (w, eid), so any order-preserving map that keeps ties tied gives the
+ * same flags: d_ranks[i] = the dense rank of d_weights[i] among the DISTINCT values of the whole
+ * array (0 the smallest, *distinct - 1 the largest, equal values equal ranks) — bit for bit
+ * np.searchsorted(np.unique(w), w), the host path's map (graph.canonicalize). -0.0 and +0.0 are one
+ * value, +-inf ordinary values, denormals distinct values; float64 is never narrowed. d_ranks is what
+ * ghs_canonicalize_device takes as d_rw (the raw weights, before the canonicalisation).
+ * d_weights: m elements of the type `wtype` names, aligned to their own size only (slices are fine);
+ * d_ranks: m uint32, 4-byte aligned, not overlapping d_weights or d_temp; d_temp: 16-byte aligned,
+ * ghs_weight_ranks_temp_bytes(wtype, m) bytes (12 B per weight for float32, 24 B otherwise, + the
+ * sort's storage; computed on the host, no GPU needed; 0 for m = 0).
+ * Pipeline: a key pass (an unsigned key that orders as the value does, value = index), a rocPRIM
+ * pairs sort over 32 (float32) or 64 key bits, head flags over the sorted keys and a scatter of every
+ * element's head count to d_ranks[index]. Everything is enqueued on `stream`; the call returns after
+ * ONE stream synchronise that brings back *distinct and the NaN flag together.
+ * Errors, checked before any device work (so GHS_E_ARG, not GHS_E_NODEVICE, on a host without GPU):
+ * unknown wtype, NULL / misaligned / overlapping pointers, m >= 2^32: GHS_E_ARG; temp_bytes short:
+ * GHS_E_NOMEM. m == 0: GHS_OK, *distinct = 0, no device work, pointers may be NULL. After the sync: a
+ * NaN anywhere: GHS_E_ARG ("NaN weight"; the ranks are then unspecified, nothing was read or written
+ * out of bounds). */
+#define GHS_W_FLOAT32 0u
+#define GHS_W_FLOAT64 1u
+#define GHS_W_INT64   2u
+#define GHS_W_UINT64  3u
+size_t ghs_weight_ranks_temp_bytes(uint32_t wtype, uint64_t m);
+int ghs_weight_ranks_device(uint32_t wtype, uint64_t m, const void *d_weights, uint32_t *d_ranks,
+                            uint64_t *distinct /* host */, void *d_temp, size_t temp_bytes, void *stream);
+
 /* device-side canonicity check: *ok = 1 iff u < v < n and (u, v) strictly ascending */
 int ghs_check_canonical(uint32_t n, uint64_t m, const uint32_t *d_u, const uint32_t *d_v, void *stream, int *ok);
 

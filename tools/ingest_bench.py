@@ -18,6 +18,17 @@ lower bound from a byte count, not a measurement.
     python tools/ingest_bench.py --scale 20 --host --out profiles/r07/ingest_bench.json
     python tools/ingest_bench.py --scale 22 --host --host-repeats 2 --out profiles/r07/ingest_bench.json
     python tools/ingest_bench.py --scale 24 --out profiles/r07/ingest_bench.json      (merges into the file)
+
+--weights {f32,f64,i64}: the weight-rank pass (device.weight_ranks) on the same raw tuples, with
+weights of that dtype (a hash of the index as the dtype's bit pattern, about a quarter of them
+repeated values). Timed the same way, same process, same input:
+  weight_ranks                 the rank pass alone
+  canonicalize_rank_weights    canonicalize_device(..., rank_weights=True): ranks + canonicalisation + gather
+  canonicalize_uint32          the uint32 canonicalize_device call on the same tuples (the yardstick)
+  host                         (--host, s20 / s22) D2H, graph.canonicalize (np.unique + searchsorted rank
+                               map, then the sort), DeviceEdges.from_host; compared array by array
+
+    python tools/ingest_bench.py --scale 22 --weights f64 --host --host-repeats 2 --out profiles/r08/ingest_weights.json
 """
 import argparse
 import ctypes
@@ -157,9 +168,129 @@ def run_scale(scale, seed, warmup, repeats, host, host_repeats):
     return rec
 
 
+W_DTYPES = {"f32": "float32", "f64": "float64", "i64": "int64"}
+
+
+def raw_weights(kind, T):
+    """T weights of the chosen dtype on the device: a hash of the index mapped into the dtype (both
+    signs, far outside [0, 2^32) for i64), about a quarter of them repeated values (index i with
+    i % 4 == 0 takes the value of index i // 64 * 64: runs of 16 equal weights spread over the list)."""
+    import torch
+    M = 0xFFFFFFFF
+
+    def mix32(x):
+        x = ((x ^ (x >> 16)) * 0x7FEB352D) & M
+        x = ((x ^ (x >> 15)) * 0x846CA68B) & M
+        return x ^ (x >> 16)
+
+    idx = torch.arange(T, dtype=torch.int64, device="cuda")
+    idx = torch.where(idx % 4 == 0, idx // 64 * 64, idx)
+    lo, hi = mix32(idx ^ 0x2545F491), mix32(idx ^ 0x68E31DA4)
+    del idx
+    # the hash as the dtype's bit pattern: every sign, exponent (denormals too) and mantissa bit in
+    # play; an all-ones exponent (inf / NaN) gets its top exponent bit cleared
+    if kind == "f32":
+        lo = torch.where((lo & 0x7F800000) == 0x7F800000, lo & ~0x40000000, lo)
+        w = torch.where(lo >= (1 << 31), lo - (1 << 32), lo).to(torch.int32).view(torch.float32)
+    else:
+        w = ((hi - (1 << 31)) << 32) | lo
+        if kind == "f64":
+            e = 0x7FF0000000000000
+            w = torch.where((w & e) == e, w & ~(1 << 62), w).view(torch.float64)
+    del lo, hi
+    torch.cuda.synchronize()
+    return w
+
+
+def weight_bytes_per_edge(kind):
+    """HBM bytes per weight of the rank pass (DESIGN.md "Weight ranks on the device")."""
+    kb = 4 if kind == "f32" else 8
+    digits = 8 * kb // SORT_DIGIT_BITS
+    return {
+        "k_weight_keys": kb + kb + 4,       # reads the weight; writes key + index
+        "sort_histogram": kb,               # one read of the keys
+        "sort_digits": digits * 2 * (kb + 4),  # per digit: a (key, index) pair read and written
+        "k_rank_count": kb,                 # the sorted keys
+        "k_rank_write": kb + 4 + 4,         # keys, indices; a 4-byte scatter per element
+        "digits": digits,
+    }
+
+
+def run_weights(scale, seed, warmup, repeats, host, host_repeats, kind):
+    """The rank pass on `kind` weights against the uint32 canonicalize_device call on the same raw
+    tuples (and, with --host, against graph.canonicalize's host rank map + sort)."""
+    import numpy as np
+    import torch
+
+    from distributed_ghs_implementation_amd import canonicalize
+    from distributed_ghs_implementation_amd.device import DeviceEdges, canonicalize_device, weight_ranks
+    assert torch.cuda.is_available(), "ingest_bench needs a GPU (no fallback)"
+    n, T = 1 << scale, EF << scale
+    u, v, w32 = raw_rmat(scale, seed)
+    w = raw_weights(kind, T)
+    sync = torch.cuda.synchronize
+    keep = {}
+
+    def ranks():
+        keep["r"] = weight_ranks(w)
+    t_rank = timed(ranks, warmup, repeats, sync)
+    distinct = keep.pop("r")[1]
+
+    def whole():
+        keep["e"] = canonicalize_device(n, u, v, w, rank_weights=True)
+    t_whole = timed(whole, warmup, repeats, sync)
+    e = keep["e"]
+
+    def u32():
+        keep["c"] = canonicalize_device(n, u, v, w32)
+    t_u32 = timed(u32, warmup, repeats, sync)
+    assert keep.pop("c").m == e.m
+    med = statistics.median
+    print(f"s{scale} {kind}: weight_ranks {med(t_rank) * 1e3:.3f} ms, ranked canonicalize {med(t_whole) * 1e3:.3f} ms, "
+          f"uint32 canonicalize {med(t_u32) * 1e3:.3f} ms, distinct = {distinct} of {T}", file=sys.stderr, flush=True)
+    bpe = weight_bytes_per_edge(kind)
+    total_b = sum(x for k, x in bpe.items() if k != "digits") * T
+    rec = {
+        "workload": f"rmat-s{scale}-ef{EF}-raw", "weights": W_DTYPES[kind], "n": n, "m_raw": T, "m": e.m, "seed": seed,
+        "distinct": distinct, "repeated_fraction": 1.0 - distinct / T,
+        "weight_ranks": spread(t_rank), "canonicalize_rank_weights": spread(t_whole),
+        "canonicalize_uint32": spread(t_u32),
+        "ratio_ranks_over_uint32_canonicalize": med(t_rank) / med(t_u32),
+        "ratio_ranked_over_uint32_canonicalize": med(t_whole) / med(t_u32),
+        "bytes_per_weight": bpe,
+        "bound": {"bytes": total_b, "ms_at_spec_8.0TBs": total_b / (HBM_SPEC_TBS * 1e12) * 1e3,
+                  "ms_at_copy_6.29TBs": total_b / (HBM_COPY_TBS * 1e12) * 1e3,
+                  "note": "bytes / HBM rate: a lower bound, not a measurement"},
+        "host": None,
+    }
+    if host:
+        def host_path():
+            hu, hv = (t.cpu().numpy().view("uint32") for t in (u, v))
+            hw = w.cpu().numpy()
+            t1 = time.perf_counter()
+            g = canonicalize(n, u=hu, v=hv, w=hw)
+            t2 = time.perf_counter()
+            keep["h"], keep["g"] = DeviceEdges.from_host(g), g
+            keep["sort_s"] = t2 - t1
+            print(f"s{scale} {kind}: host canonicalize {t2 - t1:.2f} s", file=sys.stderr, flush=True)
+        t_host = timed(host_path, 0, host_repeats, sync)
+        h, g = keep["h"], keep["g"]
+        equal = bool(h.m == e.m and all(torch.equal(a, b) for a, b in zip((e.u, e.v, e.w), (h.u, h.v, h.w)))
+                     and np.array_equal(e.weights.cpu().numpy(), g.weights))
+        assert equal, "device and host rank-mapped canonical lists differ"
+        rec["host"] = dict(spread(t_host), equal_to_device=equal, last_canonicalize_s=keep["sort_s"])
+        rec["ratio_host_over_device"] = med(t_host) / med(t_whole)
+        rec["ratio_host_over_device_worst"] = min(t_host) / max(t_whole)
+    else:
+        rec["host_note"] = "not measured (--host, at s20 / s22)"
+    return rec
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--scale", type=int, required=True)
+    ap.add_argument("--weights", choices=sorted(W_DTYPES), default=None,
+                    help="time the weight-rank pass on float32 / float64 / int64 weights instead")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=7)
@@ -167,14 +298,17 @@ def main(argv=None):
     ap.add_argument("--host-repeats", type=int, default=3)
     ap.add_argument("--out", type=str, default=None, help="JSON file to merge the scale into")
     args = ap.parse_args(argv)
-    rec = run_scale(args.scale, args.seed, args.warmup, args.repeats, args.host, args.host_repeats)
+    if args.weights:
+        rec = run_weights(args.scale, args.seed, args.warmup, args.repeats, args.host, args.host_repeats, args.weights)
+    else:
+        rec = run_scale(args.scale, args.seed, args.warmup, args.repeats, args.host, args.host_repeats)
     print(json.dumps(rec))
     if args.out:
         doc = {}
         if os.path.exists(args.out):
             with open(args.out) as f:
                 doc = json.load(f)
-        doc[f"s{args.scale}"] = rec
+        doc[f"s{args.scale}-{args.weights}" if args.weights else f"s{args.scale}"] = rec
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump(doc, f, indent=2, sort_keys=True)
