@@ -10,6 +10,9 @@
     --output FILE  result path (default <graph-dir>/ghs_mst.json)
     --check        verify the result after the run (verify.py: forest, spans every component,
                    weight vs NetworkX when available — the reference's check_mst.py)
+    --check-device verify the result on the GPU, exactly, at any size (verify.verify_forest_device:
+                   the flags equal canonical Kruskal's under the key (w, eid)); prints the counts
+                   and CORRECT / INCORRECT, exit status 1 when not ok
     --check-result FILE
                    verify an existing result JSON against the graph; no GPU, no solve
 
@@ -106,6 +109,8 @@ def main(argv=None):
     ap.add_argument("--mpi-compat", action="store_true")
     ap.add_argument("--quiet", action="store_true")
     ap.add_argument("--check", action="store_true", help="verify the result (check_mst.py)")
+    ap.add_argument("--check-device", action="store_true",
+                    help="verify the result on the GPU: exact optimality at any size (device verifier)")
     ap.add_argument("--check-result", type=str, default=None, help="verify an existing result JSON only")
     ap.add_argument("--gpus", type=int, default=1, help="GPUs driven by this one process (RCCL clique)")
     ap.add_argument("--generator", choices=["rmat", "grid"], default=None, help="synthetic graph instead of a file")
@@ -154,12 +159,14 @@ def main(argv=None):
         in_mst = d.in_mst_host()
         triples = g.edge_triples(in_mst)
         rounds, ms = res.rounds, res.ms_total
+        flags = in_mst
         dist.barrier()
         dist.destroy_process_group()
     else:
         from .mst import minimum_spanning_forest
         r = minimum_spanning_forest(g, num_gpus=args.gpus)
         triples, rounds, ms = r.triples(), r.rounds, r.ms_total
+        flags = r.in_mst
     if rank != 0:
         return 0
     if args.output:
@@ -183,12 +190,18 @@ def main(argv=None):
         else:
             print(f"Spanning forest: {g.n - res['num_edges']} components")
         print(f"Results saved to: {out}")
+    status = 0
     if args.check:
         from .verify import format_report, verify_forest
         rep = verify_forest(g, triples)
         print(format_report(rep, triples))
-        return 0 if rep["ok"] else 1
-    return 0
+        status = 0 if rep["ok"] else 1
+    if args.check_device:
+        from .verify import format_device_report, verify_forest_device
+        drep = verify_forest_device(g, flags)
+        print(format_device_report(drep))
+        status = status if drep["ok"] else 1
+    return status
 
 
 if __name__ == "__main__":

@@ -56,6 +56,7 @@ EXPORTED_SYMBOLS = (
     "ghs_batch_workspace_bytes", "ghs_mst_batch_device", "ghs_mst_batch_host",
     "ghs_canonicalize_temp_bytes", "ghs_canonicalize_device",
     "ghs_weight_ranks_temp_bytes", "ghs_weight_ranks_device",
+    "ghs_verify_workspace_bytes", "ghs_verify_msf_device",
 )
 
 
@@ -143,6 +144,29 @@ class BatchResult(ctypes.Structure):
         ("status", ctypes.c_uint32),  # 0 ok, 1 not canonical, 2 round cap, 3 over the size caps
         ("reserved", ctypes.c_uint32),
     ]
+
+
+class VerifyResult(ctypes.Structure):
+    """ghs_verify_result_t: the device verifier's verdict (ghs_verify_msf_device)."""
+    _fields_ = [
+        ("ok", ctypes.c_uint32),
+        ("rounds", ctypes.c_uint32),
+        ("overfull", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+        ("tree_edges", ctypes.c_uint64),
+        ("components", ctypes.c_uint64),
+        ("total_weight", ctypes.c_uint64),
+        ("cyclic_edges", ctypes.c_uint64),
+        ("unspanned_edges", ctypes.c_uint64),
+        ("lighter_edges", ctypes.c_uint64),
+        ("first_bad_eid", ctypes.c_uint64),  # UINT64_MAX: none
+        ("ms_total", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+        d["ok"], d["overfull"] = bool(d["ok"]), bool(d["overfull"])
+        return d
 
 
 # the same layout as a numpy structured dtype (a device buffer of results viewed on the host)
@@ -332,6 +356,9 @@ def load():
             # ABI 10 addition: float / 64-bit weights -> dense ranks (the uint32 engine weights)
             "ghs_weight_ranks_temp_bytes": (sz, [u32, u64]),
             "ghs_weight_ranks_device": (i32, [u32, u64, vp, vp, P(u64), vp, sz, vp]),
+            # ABI 10 addition: the device verifier (flags == the MSF, exactly)
+            "ghs_verify_workspace_bytes": (sz, [u32, u64]),
+            "ghs_verify_msf_device": (i32, [u32, u64, vp, vp, vp, vp, vp, sz, vp, P(VerifyResult)]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(L, name)

@@ -403,6 +403,50 @@ class DeviceMST:
     def in_mst_host(self):
         return self.in_mst[: self.edges.m].cpu().numpy().astype(bool)
 
+    def verify(self):
+        """`verify_msf` of the engine's own flags (after `run()`)."""
+        return verify_msf(self.edges, self.in_mst)
+
+
+def verify_msf(edges, in_mst):
+    """Is `in_mst` THE minimum spanning forest of `edges`? Checked on the device, exactly, without a
+    second solve (ghs_verify_msf_device: Boruvka over the flagged edges alone, then one walk per edge
+    of the graph up the Boruvka tree — csrc/verify.hip, which shares no code with the solver).
+    edges: a DeviceEdges with `u` present (a CSR-only list raises ValueError); in_mst: a uint8 / bool
+    GPU tensor of at least m flags (nonzero = in the MSF), only read. Returns the fields of
+    ghs_verify_result_t as a dict: ok, rounds, overfull, tree_edges, components, total_weight,
+    cyclic_edges, unspanned_edges, lighter_edges, first_bad_eid, ms_total. ok is True iff the flags
+    equal canonical Kruskal's under the key (w, eid), byte for byte. Runs on torch's current stream; a
+    non-canonical list raises GHSError (GHS_E_NONCANON)."""
+    if edges.u is None:
+        raise ValueError("verify_msf needs the COO form (u present); a CSR-only list is not supported")
+    if not isinstance(in_mst, torch.Tensor) or in_mst.dim() != 1:
+        raise ValueError("in_mst: a one-dimensional GPU tensor of flags expected")
+    if in_mst.dtype == torch.bool:
+        in_mst = in_mst.view(torch.uint8)
+    if in_mst.dtype != torch.uint8:
+        raise ValueError(f"in_mst: uint8 or bool flags expected, got {in_mst.dtype}")
+    n, m = edges.n, edges.m
+    if in_mst.numel() < m:
+        raise ValueError(f"in_mst holds {in_mst.numel()} flags, the edge list {m} edges")
+    L = _native.load()
+    res = _native.VerifyResult()
+    if m == 0:
+        _native.check(L.ghs_verify_msf_device(n, 0, None, None, None, None, None, 0, None, ctypes.byref(res)))
+        return res.as_dict()
+    _native.require_gpu()
+    if not in_mst.is_cuda or in_mst.device != edges.device:
+        raise ValueError("in_mst must be on the edge list's device")
+    if in_mst.stride(0) != 1:
+        in_mst = in_mst.contiguous()
+    with torch.cuda.device(edges.device):
+        ws_bytes = int(L.ghs_verify_workspace_bytes(n, m))
+        ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=edges.device)
+        _native.check(L.ghs_verify_msf_device(n, m, _ptr(edges.u), _ptr(edges.v), _ptr(edges.w), _ptr(in_mst),
+                                              _ptr(ws), ws_bytes, _stream(), ctypes.byref(res)))
+    del ws
+    return res.as_dict()
+
 
 class DeviceBatch:
     """Many small graphs in batch-canonical form as torch tensors (int32 holding uint32 bit

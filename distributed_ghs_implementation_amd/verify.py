@@ -11,11 +11,48 @@ graph edge with the same weight, the result is a forest (components(T) == n - |T
 every component of the graph (components(T) == components(G)). Optimality is checked against
 NetworkX (the reference's own verifier; third-party, optional) when it is importable and the
 graph is small enough for it (`nx_max_edges`); otherwise `weight_matches_networkx` is None.
-This module never calls the HIP engine, so it also verifies results produced elsewhere.
+These host checks never call the HIP engine, so they also verify results produced elsewhere.
+
+`verify_forest_device` is the one function here that needs a GPU: it checks optimality exactly at
+any size (flags == canonical Kruskal's under the key (w, eid)) with the device verifier
+(ghs_verify_msf_device, csrc/verify.hip — independent of the solver's kernels), where the NetworkX
+comparison stops at `NX_MAX_EDGES`.
 """
 import numpy as np
 
 NX_MAX_EDGES = 2_000_000  # NetworkX needs ~0.9 GB per 1M edges (SURVEY.md 8(d))
+
+
+def verify_forest_device(graph, in_mst):
+    """Check the flags `in_mst` (m host bools / bytes, nonzero = in the MSF) of the host
+    CanonicalGraph `graph` on the GPU: one H2D copy (DeviceEdges.from_host), then
+    device.verify_msf. Returns its dict (ok, cyclic_edges, unspanned_edges, lighter_edges,
+    tree_edges, components, total_weight, first_bad_eid, ...); ok is True iff the flags are the MSF
+    canonical Kruskal selects, byte for byte. Raises without the HIP library or a GPU."""
+    import torch
+
+    from . import _native
+    from .device import DeviceEdges, verify_msf
+    flags = np.ascontiguousarray(np.asarray(in_mst) != 0).view(np.uint8)
+    if flags.ndim != 1 or len(flags) != graph.m:
+        raise ValueError(f"in_mst holds {flags.size} flags, the graph {graph.m} edges")
+    _native.load()
+    if graph.m:
+        _native.require_gpu()
+    dev = "cuda" if graph.m else "cpu"
+    return verify_msf(DeviceEdges.from_host(graph, device=dev), torch.from_numpy(flags.copy()).to(dev))
+
+
+def format_device_report(rep):
+    """The device verifier's counts and verdict as text (the --check-device output)."""
+    first = "none" if rep["first_bad_eid"] == (1 << 64) - 1 else str(rep["first_bad_eid"])
+    lines = [f"Device verifier: tree edges {rep['tree_edges']}  components {rep['components']}  "
+             f"total weight {rep['total_weight']}  rounds {rep['rounds']}  {rep['ms_total']:.3f} ms",
+             f"  cyclic edges: {rep['cyclic_edges']}{' (overfull: lower bound)' if rep['overfull'] else ''}  "
+             f"unspanned edges: {rep['unspanned_edges']}  lighter edges: {rep['lighter_edges']}  "
+             f"first bad edge id: {first}",
+             f"Status: {'CORRECT' if rep['ok'] else 'INCORRECT'}"]
+    return "\n".join(lines)
 
 
 def _components(n, a, b):

@@ -324,6 +324,51 @@ size_t ghs_weight_ranks_temp_bytes(uint32_t wtype, uint64_t m);
 int ghs_weight_ranks_device(uint32_t wtype, uint64_t m, const void *d_weights, uint32_t *d_ranks,
                             uint64_t *distinct /* host */, void *d_temp, size_t temp_bytes, void *stream);
 
+/* ---- device verifier: is this flag vector THE MSF? (ABI 10 addition) -------------------------
+ * Replaces the reference's check of a run against a recomputed NetworkX MST (check_mst.py:1-20,
+ * ghs_implementation.py:746) at every size the engine solves, on the device, exactly, and without a
+ * second solve: csrc/verify.hip shares no code with the solver and launches none of its kernels.
+ * Let T be the flagged edges (a nonzero flag byte means "in the MSF", as in ghs_flags_to_eids) and
+ * F = MSF(T) under the strict key (w, eid); if T is a forest, F = T.
+ *   cyclic_edges    = |T| - |F|: flagged edges that close a cycle;
+ *   unspanned_edges = edges of G (flagged or not) whose ends lie in different components of T;
+ *   lighter_edges   = unflagged edges whose ends lie in one component of T and whose key is smaller
+ *                     than the largest key on the F-path between its ends.
+ * ok = all three are 0. Keys are distinct, so the MSF is unique: cyclic = 0 makes T a forest,
+ * unspanned = 0 makes it span every component of G, lighter = 0 is the cycle property for every
+ * non-tree edge — hence ok <=> the flags equal canonical Kruskal's, byte for byte. This is not a
+ * weight comparison: a forest of the right total weight with the wrong tie-break fails it.
+ * Method (King's Boruvka-tree lemma): plain Boruvka over T alone (|T| <= n - 1); every fragment f
+ * alive at round r leaves a 16-byte node {the key f chose in round r, the dense id of its fragment at
+ * round r + 1}; a fragment with no outgoing T-edge is finished (parent NONE) and dropped. Unfinished
+ * fragments at least halve per round, so all levels hold <= 2n nodes. The largest key on the F-path
+ * between u and v is the largest key met while walking both ends up the levels until they meet; one
+ * kernel walks all m edges (an end that reaches a finished fragment first is in another component).
+ * tree_edges = |T|, components = n - |F|, total_weight = the sum of w over T, rounds = Boruvka
+ * rounds over T, first_bad_eid = the smallest eid counted in any of the three (UINT64_MAX if none).
+ * d_in_mst (m bytes, any alignment) is only read. Work is enqueued on `stream`; the call returns once
+ * *result is final (one host sync per round, <= 33, + 2). The workspace holds at most min(m, n - 1)
+ * tree edges: if more are flagged the call returns GHS_OK with ok = 0, overfull = 1, tree_edges exact
+ * and cyclic_edges = tree_edges - (n - 1) as a lower bound; the other counts are then unspecified.
+ * Workspace: 32 B per vertex of nodes + 9 B per vertex + 32 B per possible tree edge (computed on
+ * the host, no GPU needed). A verdict of ok = 0 is a result, not an error code.
+ * Errors, checked before any device work (so they hold on a host without GPU): NULL or misaligned
+ * pointers (16 bytes for u / v / w / workspace) or m >= 2^31: GHS_E_ARG; workspace_bytes short:
+ * GHS_E_NOMEM. m == 0: GHS_OK, ok = 1, components = n, no device work, pointers may be NULL. A
+ * non-canonical list (ghs_check_canonical): GHS_E_NONCANON before any index is formed from it.
+ * GHS_E_ROUNDCAP: the round-cap guard (never expected). */
+typedef struct ghs_verify_result {   /* 80 bytes */
+  uint32_t ok, rounds, overfull, reserved;
+  uint64_t tree_edges, components, total_weight;
+  uint64_t cyclic_edges, unspanned_edges, lighter_edges;
+  uint64_t first_bad_eid;            /* smallest eid counted above, UINT64_MAX if none */
+  double ms_total;                   /* host wall time of the call */
+} ghs_verify_result_t;
+size_t ghs_verify_workspace_bytes(uint32_t n, uint64_t m);   /* host only, no GPU needed */
+int ghs_verify_msf_device(uint32_t n, uint64_t m, const uint32_t *d_u, const uint32_t *d_v,
+                          const uint32_t *d_w, const uint8_t *d_in_mst, void *d_workspace,
+                          size_t workspace_bytes, void *stream, ghs_verify_result_t *result);
+
 /* device-side canonicity check: *ok = 1 iff u < v < n and (u, v) strictly ascending */
 int ghs_check_canonical(uint32_t n, uint64_t m, const uint32_t *d_u, const uint32_t *d_v, void *stream, int *ok);
 
