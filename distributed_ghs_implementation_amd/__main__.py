@@ -15,6 +15,11 @@
                    and CORRECT / INCORRECT, exit status 1 when not ok
     --check-result FILE
                    verify an existing result JSON against the graph; no GPU, no solve
+    --labels OUT.npy
+                   after the solve, write every vertex's cluster as a numpy uint32 array (the forest's
+                   components labelled on the GPU, clusters ordered by their smallest vertex); with
+                   --clusters K the heaviest forest edges are dropped until K clusters remain, with
+                   --max-weight T only forest edges of weight <= T are kept (single linkage)
 
     --batch-dir ROOT
                    many small graphs in one launch: every immediate subdirectory of ROOT holding
@@ -112,11 +117,20 @@ def main(argv=None):
     ap.add_argument("--check-device", action="store_true",
                     help="verify the result on the GPU: exact optimality at any size (device verifier)")
     ap.add_argument("--check-result", type=str, default=None, help="verify an existing result JSON only")
+    ap.add_argument("--labels", type=str, default=None, metavar="OUT.npy",
+                    help="write the vertices' cluster labels (uint32 .npy) after the solve")
+    ap.add_argument("--clusters", type=int, default=None, help="with --labels: single linkage into K clusters")
+    ap.add_argument("--max-weight", type=float, default=None,
+                    help="with --labels: keep forest edges of weight <= T (single linkage at distance T)")
     ap.add_argument("--gpus", type=int, default=1, help="GPUs driven by this one process (RCCL clique)")
     ap.add_argument("--generator", choices=["rmat", "grid"], default=None, help="synthetic graph instead of a file")
     ap.add_argument("--scale", type=int, default=16, help="R-MAT scale (2^scale vertices) / grid side k")
     ap.add_argument("--seed", type=int, default=1, help="generator seed (weights: seed + 1)")
     args = ap.parse_args(argv)
+    if args.clusters is not None and args.max_weight is not None:
+        ap.error("--clusters and --max-weight exclude each other")
+    if (args.clusters is not None or args.max_weight is not None) and not args.labels:
+        ap.error("--clusters / --max-weight need --labels OUT.npy")
     if args.batch_dir is not None:
         return run_batch_dir(args)
 
@@ -190,6 +204,23 @@ def main(argv=None):
         else:
             print(f"Spanning forest: {g.n - res['num_edges']} components")
         print(f"Results saved to: {out}")
+    if args.labels:
+        import numpy as np
+
+        from .mst import MSTResult
+        lr = MSTResult(g, np.asarray(flags), 0, rounds, [], ms)
+        t = args.max_weight
+        if t is not None and g.weights is None:
+            # integer engine weights: floor(T), and a negative T keeps nothing (as n clusters do)
+            t = None if t < 0 else int(min(t, float((1 << 32) - 1)))
+        if args.max_weight is not None and t is None:
+            labels, info = lr.labels(num_clusters=max(g.n, 1), return_info=True)
+        else:
+            labels, info = lr.labels(max_weight=t, num_clusters=args.clusters, return_info=True)
+        np.save(args.labels, labels)
+        if not args.quiet:
+            print(f"Clusters: {info['num_clusters']} (kept {info['kept_edges']} of {info['flagged_edges']} forest edges)")
+            print(f"Labels saved to: {args.labels}")
     status = 0
     if args.check:
         from .verify import format_report, verify_forest

@@ -29,6 +29,10 @@ GHS_W_FLOAT32 = 0
 GHS_W_FLOAT64 = 1
 GHS_W_INT64 = 2
 GHS_W_UINT64 = 3
+# ghs_forest_labels_device's cut modes (include/ghs_mst.h GHS_CUT_*)
+GHS_CUT_NONE = 0
+GHS_CUT_WEIGHT = 1
+GHS_CUT_COUNT = 2
 
 _ERR_NAMES = {
     GHS_E_ARG: "GHS_E_ARG", GHS_E_NONCANON: "GHS_E_NONCANON", GHS_E_HIP: "GHS_E_HIP",
@@ -57,6 +61,7 @@ EXPORTED_SYMBOLS = (
     "ghs_canonicalize_temp_bytes", "ghs_canonicalize_device",
     "ghs_weight_ranks_temp_bytes", "ghs_weight_ranks_device",
     "ghs_verify_workspace_bytes", "ghs_verify_msf_device",
+    "ghs_forest_labels_workspace_bytes", "ghs_forest_labels_device", "ghs_forest_labels_host",
 )
 
 
@@ -166,6 +171,26 @@ class VerifyResult(ctypes.Structure):
     def as_dict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
         d["ok"], d["overfull"] = bool(d["ok"]), bool(d["overfull"])
+        return d
+
+
+class LabelsResult(ctypes.Structure):
+    """ghs_labels_result_t: what ghs_forest_labels_device / ghs_forest_labels_host found."""
+    _fields_ = [
+        ("flagged_edges", ctypes.c_uint64),
+        ("kept_edges", ctypes.c_uint64),
+        ("dropped_edges", ctypes.c_uint64),
+        ("num_clusters", ctypes.c_uint64),
+        ("cut_key", ctypes.c_uint64),  # UINT64_MAX: nothing dropped by a count cut
+        ("rounds", ctypes.c_uint32),
+        ("is_forest", ctypes.c_uint32),
+        ("ms_total", ctypes.c_double),
+        ("reserved", ctypes.c_uint64),
+    ]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+        d["is_forest"] = bool(d["is_forest"])
         return d
 
 
@@ -359,6 +384,10 @@ def load():
             # ABI 10 addition: the device verifier (flags == the MSF, exactly)
             "ghs_verify_workspace_bytes": (sz, [u32, u64]),
             "ghs_verify_msf_device": (i32, [u32, u64, vp, vp, vp, vp, vp, sz, vp, P(VerifyResult)]),
+            # ABI 10 addition: vertex labels of a flagged forest, with weight / count cuts
+            "ghs_forest_labels_workspace_bytes": (sz, [u32, u64]),
+            "ghs_forest_labels_device": (i32, [u32, u64, vp, vp, vp, vp, u32, u64, vp, vp, sz, vp, P(LabelsResult)]),
+            "ghs_forest_labels_host": (i32, [u32, u64, vp, vp, vp, vp, u32, u64, vp, P(LabelsResult)]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(L, name)

@@ -43,3 +43,44 @@ extern "C" int ghs_mst_host(uint32_t n, uint64_t m, const uint32_t *u, const uin
   if (m) GHS_HIP_CHECK(hipMemcpy(in_mst, b + off_mst, m, hipMemcpyDeviceToHost));
   return GHS_OK;
 }
+
+// Host-buffer form of ghs_forest_labels_device (the nx.connected_components step a reference user runs
+// on a result, check_mst.py:1-20): copy in, run, copy out.
+extern "C" int ghs_forest_labels_host(uint32_t n, uint64_t m, const uint32_t *u, const uint32_t *v, const uint32_t *w,
+                                      const uint8_t *in_mst, uint32_t mode, uint64_t param, uint32_t *labels,
+                                      ghs_labels_result_t *result) {
+  if (!result) GHS_FAIL(GHS_E_ARG, "result is NULL");
+  *result = ghs_labels_result_t{};
+  result->cut_key = ~0ull;
+  if (mode != GHS_CUT_NONE && mode != GHS_CUT_WEIGHT && mode != GHS_CUT_COUNT) GHS_FAIL(GHS_E_ARG, "unknown cut mode");
+  if (mode == GHS_CUT_WEIGHT && param >= (1ull << 32)) GHS_FAIL(GHS_E_ARG, "GHS_CUT_WEIGHT: the threshold must be < 2^32");
+  if (mode == GHS_CUT_COUNT && param == 0) GHS_FAIL(GHS_E_ARG, "GHS_CUT_COUNT: k must be >= 1");
+  if (n == 0) {
+    result->is_forest = 1;
+    return GHS_OK;
+  }
+  if (m >= (1ull << 31)) GHS_FAIL(GHS_E_ARG, "m must be < 2^31");
+  if (!labels || (m && (!u || !v || !w || !in_mst))) GHS_FAIL(GHS_E_ARG, "NULL host pointer");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) GHS_FAIL(GHS_E_NODEVICE, "no HIP device");
+  const size_t ws = m ? ghs_forest_labels_workspace_bytes(n, m) : 0;
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t off_u = 0, off_v = off_u + al(m * 4), off_w = off_v + al(m * 4), off_f = off_w + al(m * 4),
+               off_l = off_f + al(m ? m : 1), off_ws = off_l + al((size_t)n * 4), total = off_ws + al(ws ? ws : 1);
+  DevBuf buf;
+  GHS_HIP_CHECK(hipMalloc(&buf.p, total));
+  char *b = (char *)buf.p;
+  hipStream_t st = nullptr;
+  if (m) {
+    GHS_HIP_CHECK(hipMemcpyAsync(b + off_u, u, m * 4, hipMemcpyHostToDevice, st));
+    GHS_HIP_CHECK(hipMemcpyAsync(b + off_v, v, m * 4, hipMemcpyHostToDevice, st));
+    GHS_HIP_CHECK(hipMemcpyAsync(b + off_w, w, m * 4, hipMemcpyHostToDevice, st));
+    GHS_HIP_CHECK(hipMemcpyAsync(b + off_f, in_mst, m, hipMemcpyHostToDevice, st));
+  }
+  int rc = ghs_forest_labels_device(n, m, (uint32_t *)(b + off_u), (uint32_t *)(b + off_v), (uint32_t *)(b + off_w),
+                                    (uint8_t *)(b + off_f), mode, param, (uint32_t *)(b + off_l), b + off_ws, ws, st,
+                                    result);
+  if (rc) return rc;
+  GHS_HIP_CHECK(hipMemcpy(labels, b + off_l, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return GHS_OK;
+}

@@ -407,6 +407,11 @@ class DeviceMST:
         """`verify_msf` of the engine's own flags (after `run()`)."""
         return verify_msf(self.edges, self.in_mst)
 
+    def labels(self, max_weight=None, num_clusters=None):
+        """`forest_labels` of the engine's own flags (after `run()`): with no cut, the connected
+        components of the graph."""
+        return forest_labels(self.edges, self.in_mst, max_weight=max_weight, num_clusters=num_clusters)
+
 
 def verify_msf(edges, in_mst):
     """Is `in_mst` THE minimum spanning forest of `edges`? Checked on the device, exactly, without a
@@ -446,6 +451,118 @@ def verify_msf(edges, in_mst):
                                               _ptr(ws), ws_bytes, _stream(), ctypes.byref(res)))
     del ws
     return res.as_dict()
+
+
+def _int_threshold(t, lo, hi):
+    """floor(t) clamped to [lo - 1, hi] as a Python int (lo - 1: below every value of the range)."""
+    import math
+    import numbers
+    if not isinstance(t, numbers.Integral):
+        t = float(t)
+        if math.isnan(t):
+            raise ValueError("max_weight must not be NaN")
+        if math.isinf(t):
+            return hi if t > 0 else lo - 1
+        t = math.floor(t)
+    return max(lo - 1, min(hi, int(t)))
+
+
+def _rank_threshold(edges, max_weight):
+    """The largest engine weight (rank) among the edges whose own weight is <= max_weight, found on
+    the device; None when no edge qualifies. Integer weights are compared as integers (exact at any
+    magnitude), float weights as float64 / float32 values."""
+    wt = edges.weights
+    if wt.numel() == 0:
+        return None
+    if hasattr(torch, "uint64") and wt.dtype == torch.uint64:
+        t = _int_threshold(max_weight, 0, (1 << 64) - 1)
+        if t < 0:
+            return None
+        ok = (wt.view(torch.int64) ^ (-(1 << 63))) <= (t - (1 << 63))  # order of uint64 on int64 bits
+    elif not wt.dtype.is_floating_point:
+        t = _int_threshold(max_weight, -(1 << 63), (1 << 63) - 1)
+        if t < -(1 << 63):
+            return None
+        ok = wt <= t
+    else:
+        t = float(max_weight)
+        if t != t:
+            raise ValueError("max_weight must not be NaN")
+        ok = wt.to(torch.float64) <= t
+    ranks = edges.w.to(torch.int64) & 0xFFFFFFFF
+    best = int(torch.where(ok, ranks, torch.full_like(ranks, -1)).max())
+    return None if best < 0 else best
+
+
+def forest_labels(edges, in_mst, max_weight=None, num_clusters=None):
+    """Label every vertex by its component of the flagged forest, on the device
+    (ghs_forest_labels_device, csrc/labels.hip): the flagged edges T, optionally cut, then min-root
+    hooking and a dense ranking of the roots. No cut: with the engine's flags, the connected
+    components of the graph. max_weight=t: only flagged edges with weight <= t are kept — single
+    linkage at distance t. num_clusters=k >= 1: the heaviest flagged edges under (w, eid) are dropped
+    until k clusters remain (never fewer than the forest has components) — single linkage into k
+    clusters. Giving both raises ValueError.
+    edges: a DeviceEdges with `u` present (a CSR-only list raises ValueError); in_mst: a uint8 / bool
+    GPU tensor of at least m flags (nonzero = in T), only read; it need not be a forest, but more
+    than min(m, n - 1) flags raise GHSError (GHS_E_ARG). max_weight is an integer in [0, 2^32) — or,
+    when `edges.weights` is set (rank-mapped weights), a value in the caller's own units, mapped on the
+    device to the largest rank whose value is <= it (none: every flagged edge is dropped).
+    Returns (labels, info): labels an int32 GPU tensor of n entries holding uint32 bit patterns —
+    the rank of the vertex's cluster, clusters ordered by their smallest vertex, so vertex 0 has label
+    0 and labels are dense in [0, num_clusters); info the fields of ghs_labels_result_t as a dict:
+    flagged_edges, kept_edges, dropped_edges, num_clusters, cut_key, rounds, is_forest, ms_total.
+    Runs on torch's current stream; a non-canonical list raises GHSError (GHS_E_NONCANON)."""
+    if edges.u is None:
+        raise ValueError("forest_labels needs the COO form (u present); a CSR-only list is not supported")
+    if not isinstance(in_mst, torch.Tensor) or in_mst.dim() != 1:
+        raise ValueError("in_mst: a one-dimensional GPU tensor of flags expected")
+    if in_mst.dtype == torch.bool:
+        in_mst = in_mst.view(torch.uint8)
+    if in_mst.dtype != torch.uint8:
+        raise ValueError(f"in_mst: uint8 or bool flags expected, got {in_mst.dtype}")
+    n, m = edges.n, edges.m
+    if in_mst.numel() < m:
+        raise ValueError(f"in_mst holds {in_mst.numel()} flags, the edge list {m} edges")
+    if max_weight is not None and num_clusters is not None:
+        raise ValueError("give max_weight or num_clusters, not both")
+    mode, param = _native.GHS_CUT_NONE, 0
+    if num_clusters is not None:
+        mode, param = _native.GHS_CUT_COUNT, int(num_clusters)
+        if param < 1:
+            raise ValueError("num_clusters must be >= 1")
+        param = min(param, (1 << 64) - 1)
+    elif max_weight is not None and edges.weights is None:
+        if int(max_weight) != max_weight or not 0 <= int(max_weight) < (1 << 32):
+            raise ValueError("max_weight must be an integer in [0, 2^32) (the list carries no rank-mapped weights)")
+        mode, param = _native.GHS_CUT_WEIGHT, int(max_weight)
+    L = _native.load()
+    _native.require_gpu()
+    if m and (not in_mst.is_cuda or in_mst.device != edges.device):
+        raise ValueError("in_mst must be on the edge list's device")
+    if m and in_mst.stride(0) != 1:
+        in_mst = in_mst.contiguous()
+    drop_all = False
+    with torch.cuda.device(edges.device):
+        if max_weight is not None and edges.weights is not None:
+            thr = _rank_threshold(edges, max_weight)
+            if thr is None:
+                # below every weight: nothing is kept. A count cut into n clusters drops exactly every
+                # flagged edge; it is reported as the weight cut it stands for (no cut key)
+                drop_all, mode, param = True, _native.GHS_CUT_COUNT, max(n, 1)
+            else:
+                mode, param = _native.GHS_CUT_WEIGHT, thr
+        res = _native.LabelsResult()
+        labels = torch.empty(n, dtype=torch.int32, device=edges.device)
+        ws_bytes = int(L.ghs_forest_labels_workspace_bytes(n, m)) if m else 0
+        ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=edges.device)
+        _native.check(L.ghs_forest_labels_device(n, m, _ptr(edges.u), _ptr(edges.v), _ptr(edges.w),
+                                                 _ptr(in_mst) if m else None, mode, param, _ptr(labels), _ptr(ws),
+                                                 ws_bytes, _stream(), ctypes.byref(res)))
+    del ws
+    info = res.as_dict()
+    if drop_all:
+        info["cut_key"] = (1 << 64) - 1
+    return labels, info
 
 
 class DeviceBatch:

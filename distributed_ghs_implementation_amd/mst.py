@@ -56,6 +56,58 @@ class MSTResult:
     def to_dict(self, algorithm="Boruvka (HIP)"):
         return mst_result_dict(self.triples(), algorithm)
 
+    def labels(self, max_weight=None, num_clusters=None, return_info=False):
+        """The cluster of every vertex as a numpy uint32 array of n entries (ghs_forest_labels_host:
+        the forest's components labelled on the GPU, clusters ordered by their smallest vertex). No
+        cut: the connected components of the graph. max_weight=t keeps the forest edges with weight
+        <= t (single linkage at distance t; for a rank-mapped graph t is in the caller's own units,
+        mapped through graph.weights); num_clusters=k drops the heaviest forest edges until k
+        clusters remain (single linkage into k clusters). return_info=True: (labels, the fields of
+        ghs_labels_result_t as a dict)."""
+        if max_weight is not None and num_clusters is not None:
+            raise ValueError("give max_weight or num_clusters, not both")
+        g = self.graph
+        mode, param, drop_all = _native.GHS_CUT_NONE, 0, False
+        if num_clusters is not None:
+            mode, param = _native.GHS_CUT_COUNT, min(int(num_clusters), (1 << 64) - 1)
+            if param < 1:
+                raise ValueError("num_clusters must be >= 1")
+        elif max_weight is not None and g.weights is None:
+            if int(max_weight) != max_weight or not 0 <= int(max_weight) < (1 << 32):
+                raise ValueError("max_weight must be an integer in [0, 2^32) (the graph's weights are not rank-mapped)")
+            mode, param = _native.GHS_CUT_WEIGHT, int(max_weight)
+        elif max_weight is not None:
+            ok = _weights_at_most(g.weights, max_weight)
+            if ok.any():
+                mode, param = _native.GHS_CUT_WEIGHT, int(g.w[ok].max())
+            else:  # below every weight: a count cut into n clusters drops exactly every forest edge
+                mode, param, drop_all = _native.GHS_CUT_COUNT, max(g.n, 1), True
+        L = _native.load()
+        _native.require_gpu()
+        flags = np.ascontiguousarray(self.in_mst, dtype=np.uint8)
+        out = np.empty(g.n, dtype=np.uint32)
+        res = _native.LabelsResult()
+        _native.check(L.ghs_forest_labels_host(g.n, g.m, g.u.ctypes.data, g.v.ctypes.data, g.w.ctypes.data,
+                                               flags.ctypes.data, mode, param, out.ctypes.data, ctypes.byref(res)))
+        info = res.as_dict()
+        if drop_all:
+            info["cut_key"] = (1 << 64) - 1
+        return (out, info) if return_info else out
+
+
+def _weights_at_most(weights, t):
+    """weights <= t as a mask; integer arrays are compared as integers, exactly at any magnitude."""
+    import math
+    if weights.dtype.kind in "iu" and not (isinstance(t, float) and (math.isinf(t) or math.isnan(t))):
+        info = np.iinfo(weights.dtype)
+        ti = math.floor(t)
+        if ti < info.min:
+            return np.zeros(len(weights), bool)
+        return weights <= weights.dtype.type(min(ti, info.max))
+    if isinstance(t, float) and math.isnan(t):
+        raise ValueError("max_weight must not be NaN")
+    return weights <= t
+
 
 def minimum_spanning_forest(graph, num_gpus=1, devices=None, config=None):
     """Run the HIP engine on a CanonicalGraph (host arrays) -> MSTResult. num_gpus > 1 (or an

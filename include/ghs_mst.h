@@ -369,6 +369,72 @@ int ghs_verify_msf_device(uint32_t n, uint64_t m, const uint32_t *d_u, const uin
                           const uint32_t *d_w, const uint8_t *d_in_mst, void *d_workspace,
                           size_t workspace_bytes, void *stream, ghs_verify_result_t *result);
 
+/* ---- vertex labels and forest cuts: which component is every vertex in? (ABI 10 addition) -----
+ * The reference has no such call: the nearest things are nx.connected_components and the nx.Graph
+ * that check_mst.py:1-20 builds from a result, both host passes over the edge list. This entry labels
+ * the vertices by the components of a flagged forest on the device, optionally after a cut — the step
+ * that turns an MSF into connected components or into a single-linkage clustering.
+ * T = the edges with a nonzero flag byte (as in ghs_flags_to_eids and the verifier); K = the kept
+ * edges after the cut; d_labels[v] = the rank of v's component of (V, K), components ordered by their
+ * smallest vertex: vertex 0 gets label 0, labels are dense in [0, num_clusters), an isolated vertex is
+ * a cluster of its own. The answer is exact and deterministic.
+ *   GHS_CUT_NONE    K = T. With the engine's flags: the connected components of the graph.
+ *   GHS_CUT_WEIGHT  K = the edges of T with w <= param: single linkage at distance param.
+ *   GHS_CUT_COUNT   param = k >= 1 target clusters: K = T minus its d heaviest edges under the key
+ *                   (w, eid), d = clamp(k - (n - |T|), 0, |T|): single linkage into k clusters. On a
+ *                   forest that gives exactly max(k, n - |T|) clusters for k <= n.
+ * T need not be a forest: the labels are the components of K whatever its shape, and is_forest says
+ * whether K closed a cycle. More than min(m, n - 1) flagged edges cannot be a forest and do not fit
+ * the workspace: GHS_E_ARG ("more flags than a forest can hold") after the count, nothing else written.
+ * Method: the flags are streamed 16 per lane (any byte alignment: scalar head and tail), the kept
+ * edges' ends gathered into a compact list (the weight cut is a predicate of that pass; the count cut
+ * a radix select of the |T| keys for the smallest one dropped, then one pass). Components by min-root
+ * hooking: par[v] = v; per round every live edge, whose ends are roots, does a read-checked
+ * atomicMin(&par[max], min); the live ends are pointer-jumped to a star forest (8 hops per launch, a
+ * launch that moved nothing ends the jumping); edges inside one tree leave the list, the others are
+ * renamed to their roots. par[x] <= x throughout, so a component's root is its smallest vertex. A
+ * root that is a local minimum and absorbs nothing in round t sees only smaller neighbours in round
+ * t + 1 and hooks then, so the roots with a live edge at least halve every two rounds:
+ * rounds <= 2 ceil(log2 n). Last: roots flagged, scanned, d_labels[v] = rank[par[v]].
+ * d_in_mst (m bytes, any alignment) is only read. Work is enqueued on `stream`; the call returns once
+ * *result and d_labels are final (one host sync per hook round + 3).
+ * Workspace (ghs_forest_labels_workspace_bytes, computed on the host, no GPU needed): 8 B per vertex
+ * (par, ranks) + 24 B per possible kept edge (two lists of ends, the keys of the count cut) + tile
+ * counts.
+ * Errors, checked before any device work (so they hold on a host without GPU): result NULL, an
+ * unknown mode, GHS_CUT_WEIGHT with param >= 2^32, GHS_CUT_COUNT with param = 0, m >= 2^31, NULL or
+ * misaligned pointers (16 bytes for u / v / w / workspace, 4 for labels): GHS_E_ARG; workspace_bytes
+ * short: GHS_E_NOMEM. n == 0: GHS_OK, nothing written. m == 0, n > 0: identity labels (one kernel;
+ * pointers other than d_labels may be NULL). A non-canonical list (ghs_check_canonical):
+ * GHS_E_NONCANON before any index is formed from it. GHS_E_ROUNDCAP: more than 80 rounds;
+ * GHS_E_STATE: two consecutive rounds did not halve the live roots (neither is ever expected). */
+#define GHS_CUT_NONE   0u   /* keep every flagged edge */
+#define GHS_CUT_WEIGHT 1u   /* keep flagged edges with w <= param (param < 2^32) */
+#define GHS_CUT_COUNT  2u   /* param = k >= 1 target clusters: drop the d heaviest flagged edges under
+                               the key (w, eid), d = clamp(k - (n - |T|), 0, |T|) */
+typedef struct ghs_labels_result {   /* 64 bytes */
+  uint64_t flagged_edges;   /* |T| */
+  uint64_t kept_edges;      /* |T| - dropped */
+  uint64_t dropped_edges;
+  uint64_t num_clusters;    /* distinct labels written */
+  uint64_t cut_key;         /* GHS_CUT_COUNT: the smallest key dropped (w << 32 | eid); UINT64_MAX if
+                               nothing was dropped or in the other modes */
+  uint32_t rounds;          /* hook rounds executed */
+  uint32_t is_forest;       /* 1 iff num_clusters == n - kept_edges (the kept edges close no cycle) */
+  double ms_total;          /* host wall time of the call */
+  uint64_t reserved;        /* 0: pads the record to 64 bytes */
+} ghs_labels_result_t;
+size_t ghs_forest_labels_workspace_bytes(uint32_t n, uint64_t m);   /* host only, no GPU needed */
+int ghs_forest_labels_device(uint32_t n, uint64_t m, const uint32_t *d_u, const uint32_t *d_v,
+                             const uint32_t *d_w, const uint8_t *d_in_mst, uint32_t mode, uint64_t param,
+                             uint32_t *d_labels /* n */, void *d_workspace, size_t workspace_bytes,
+                             void *stream, ghs_labels_result_t *result);
+/* the same for host arrays (copy in, run, copy out on the default stream); the argument errors above
+ * except the alignments, then GHS_E_NODEVICE without a GPU */
+int ghs_forest_labels_host(uint32_t n, uint64_t m, const uint32_t *u, const uint32_t *v, const uint32_t *w,
+                           const uint8_t *in_mst, uint32_t mode, uint64_t param, uint32_t *labels,
+                           ghs_labels_result_t *result);
+
 /* device-side canonicity check: *ok = 1 iff u < v < n and (u, v) strictly ascending */
 int ghs_check_canonical(uint32_t n, uint64_t m, const uint32_t *d_u, const uint32_t *d_v, void *stream, int *ok);
 
