@@ -11,6 +11,8 @@ mst.minimum_spanning_forest_batch; raw edge arrays canonicalized on the device:
 mst.minimum_spanning_forest_edges); device level: device.DeviceMST, device.batch_mst,
 device.canonicalize_device; the forest's vertex labels (connected components, single-linkage cuts by
 weight or cluster count): device.forest_labels, DeviceMST.labels, MSTResult.labels, CLI --labels;
+the forest rooted (parent, parent edge, depth, DFS preorder, subtree size per vertex):
+device.forest_root, DeviceMST.rooted, MSTResult.rooted, CLI --rooted;
 multi-GPU: distributed.DistributedMST. Float, negative and 64-bit
 weights: rank-mapped by graph.canonicalize on the host, or on the device with rank_weights=True
 (minimum_spanning_forest_edges, DeviceEdges.from_raw, canonicalize_device; device.weight_ranks).

@@ -20,6 +20,10 @@
                    components labelled on the GPU, clusters ordered by their smallest vertex); with
                    --clusters K the heaviest forest edges are dropped until K clusters remain, with
                    --max-weight T only forest edges of weight <= T are kept (single linkage)
+    --rooted OUT.npz
+                   after the solve, write the forest rooted at every tree's smallest vertex: numpy
+                   uint32 arrays parent, parent_eid (0xffffffff for a root), depth, pre (DFS preorder)
+                   and size (subtree sizes), computed on the GPU
 
     --batch-dir ROOT
                    many small graphs in one launch: every immediate subdirectory of ROOT holding
@@ -122,6 +126,8 @@ def main(argv=None):
     ap.add_argument("--clusters", type=int, default=None, help="with --labels: single linkage into K clusters")
     ap.add_argument("--max-weight", type=float, default=None,
                     help="with --labels: keep forest edges of weight <= T (single linkage at distance T)")
+    ap.add_argument("--rooted", type=str, default=None, metavar="OUT.npz",
+                    help="write the rooted forest (parent, parent_eid, depth, pre, size: uint32) after the solve")
     ap.add_argument("--gpus", type=int, default=1, help="GPUs driven by this one process (RCCL clique)")
     ap.add_argument("--generator", choices=["rmat", "grid"], default=None, help="synthetic graph instead of a file")
     ap.add_argument("--scale", type=int, default=16, help="R-MAT scale (2^scale vertices) / grid side k")
@@ -221,6 +227,15 @@ def main(argv=None):
         if not args.quiet:
             print(f"Clusters: {info['num_clusters']} (kept {info['kept_edges']} of {info['flagged_edges']} forest edges)")
             print(f"Labels saved to: {args.labels}")
+    if args.rooted:
+        import numpy as np
+
+        from .mst import MSTResult
+        rooted, rinfo = MSTResult(g, np.asarray(flags), 0, rounds, [], ms).rooted(return_info=True)
+        np.savez(args.rooted, **rooted)
+        if not args.quiet:
+            print(f"Rooted forest: {rinfo['num_trees']} trees, max depth {rinfo['max_depth']}")
+            print(f"Rooted forest saved to: {args.rooted}")
     status = 0
     if args.check:
         from .verify import format_report, verify_forest

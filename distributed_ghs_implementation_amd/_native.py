@@ -62,6 +62,7 @@ EXPORTED_SYMBOLS = (
     "ghs_weight_ranks_temp_bytes", "ghs_weight_ranks_device",
     "ghs_verify_workspace_bytes", "ghs_verify_msf_device",
     "ghs_forest_labels_workspace_bytes", "ghs_forest_labels_device", "ghs_forest_labels_host",
+    "ghs_forest_root_workspace_bytes", "ghs_forest_root_device", "ghs_forest_root_host",
 )
 
 
@@ -182,6 +183,24 @@ class LabelsResult(ctypes.Structure):
         ("dropped_edges", ctypes.c_uint64),
         ("num_clusters", ctypes.c_uint64),
         ("cut_key", ctypes.c_uint64),  # UINT64_MAX: nothing dropped by a count cut
+        ("rounds", ctypes.c_uint32),
+        ("is_forest", ctypes.c_uint32),
+        ("ms_total", ctypes.c_double),
+        ("reserved", ctypes.c_uint64),
+    ]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+        d["is_forest"] = bool(d["is_forest"])
+        return d
+
+
+class RootResult(ctypes.Structure):
+    """ghs_root_result_t: what ghs_forest_root_device / ghs_forest_root_host found."""
+    _fields_ = [
+        ("flagged_edges", ctypes.c_uint64),
+        ("num_trees", ctypes.c_uint64),
+        ("max_depth", ctypes.c_uint64),
         ("rounds", ctypes.c_uint32),
         ("is_forest", ctypes.c_uint32),
         ("ms_total", ctypes.c_double),
@@ -388,6 +407,10 @@ def load():
             "ghs_forest_labels_workspace_bytes": (sz, [u32, u64]),
             "ghs_forest_labels_device": (i32, [u32, u64, vp, vp, vp, vp, u32, u64, vp, vp, sz, vp, P(LabelsResult)]),
             "ghs_forest_labels_host": (i32, [u32, u64, vp, vp, vp, vp, u32, u64, vp, P(LabelsResult)]),
+            # ABI 10 addition: the flagged forest rooted (parent, parent edge, depth, preorder, subtree size)
+            "ghs_forest_root_workspace_bytes": (sz, [u32, u64]),
+            "ghs_forest_root_device": (i32, [u32, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, P(RootResult)]),
+            "ghs_forest_root_host": (i32, [u32, u64, vp, vp, vp, vp, vp, vp, vp, vp, P(RootResult)]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(L, name)

@@ -84,3 +84,44 @@ extern "C" int ghs_forest_labels_host(uint32_t n, uint64_t m, const uint32_t *u,
   GHS_HIP_CHECK(hipMemcpy(labels, b + off_l, (size_t)n * 4, hipMemcpyDeviceToHost));
   return GHS_OK;
 }
+
+// Host-buffer form of ghs_forest_root_device (the in_branch pointers a reference node holds after a
+// run, ghs_implementation.py:63,212): copy in, run, copy out.
+extern "C" int ghs_forest_root_host(uint32_t n, uint64_t m, const uint32_t *u, const uint32_t *v, const uint8_t *in_mst,
+                                    uint32_t *parent, uint32_t *parent_eid, uint32_t *depth, uint32_t *pre,
+                                    uint32_t *size, ghs_root_result_t *result) {
+  if (!result) GHS_FAIL(GHS_E_ARG, "result is NULL");
+  *result = ghs_root_result_t{};
+  if (n == 0) {
+    result->is_forest = 1;
+    return GHS_OK;
+  }
+  if (m >= (1ull << 31)) GHS_FAIL(GHS_E_ARG, "m must be < 2^31");
+  if (!parent || !parent_eid || !depth || (m && (!u || !v || !in_mst))) GHS_FAIL(GHS_E_ARG, "NULL host pointer");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) GHS_FAIL(GHS_E_NODEVICE, "no HIP device");
+  const size_t ws = m ? ghs_forest_root_workspace_bytes(n, m) : 0;
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t nb = al((size_t)n * 4);
+  const size_t off_u = 0, off_v = off_u + al(m * 4), off_f = off_v + al(m * 4), off_o = off_f + al(m ? m : 1),
+               off_ws = off_o + 5 * nb, total = off_ws + al(ws ? ws : 1);
+  DevBuf buf;
+  GHS_HIP_CHECK(hipMalloc(&buf.p, total));
+  char *b = (char *)buf.p;
+  hipStream_t st = nullptr;
+  if (m) {
+    GHS_HIP_CHECK(hipMemcpyAsync(b + off_u, u, m * 4, hipMemcpyHostToDevice, st));
+    GHS_HIP_CHECK(hipMemcpyAsync(b + off_v, v, m * 4, hipMemcpyHostToDevice, st));
+    GHS_HIP_CHECK(hipMemcpyAsync(b + off_f, in_mst, m, hipMemcpyHostToDevice, st));
+  }
+  uint32_t *d_out[5];
+  for (int k = 0; k < 5; ++k) d_out[k] = (uint32_t *)(b + off_o + k * nb);
+  int rc = ghs_forest_root_device(n, m, (uint32_t *)(b + off_u), (uint32_t *)(b + off_v), (uint8_t *)(b + off_f), d_out[0],
+                                  d_out[1], d_out[2], pre ? d_out[3] : nullptr, size ? d_out[4] : nullptr, b + off_ws, ws,
+                                  st, result);
+  if (rc) return rc;
+  uint32_t *h_out[5] = {parent, parent_eid, depth, pre, size};
+  for (int k = 0; k < 5; ++k)
+    if (h_out[k]) GHS_HIP_CHECK(hipMemcpy(h_out[k], d_out[k], (size_t)n * 4, hipMemcpyDeviceToHost));
+  return GHS_OK;
+}

@@ -412,6 +412,11 @@ class DeviceMST:
         components of the graph."""
         return forest_labels(self.edges, self.in_mst, max_weight=max_weight, num_clusters=num_clusters)
 
+    def rooted(self, order=True):
+        """`forest_root` of the engine's own flags (after `run()`): the MSF with every tree rooted at
+        its smallest vertex."""
+        return forest_root(self.edges, self.in_mst, order=order)
+
 
 def verify_msf(edges, in_mst):
     """Is `in_mst` THE minimum spanning forest of `edges`? Checked on the device, exactly, without a
@@ -563,6 +568,71 @@ def forest_labels(edges, in_mst, max_weight=None, num_clusters=None):
     if drop_all:
         info["cut_key"] = (1 << 64) - 1
     return labels, info
+
+
+class RootedForest:
+    """The flagged forest rooted at every tree's smallest vertex (`forest_root`): int32 GPU tensors of
+    n entries holding uint32 bit patterns. parent / parent_eid are 0xffffffff (-1 as int32) for a
+    root; pre and size are None when the call was made with order=False."""
+
+    def __init__(self, parent, parent_eid, depth, pre, size):
+        self.parent, self.parent_eid, self.depth, self.pre, self.size = parent, parent_eid, depth, pre, size
+
+    def is_ancestor(self, a, b):
+        """a is an ancestor of b, or b itself: pre[a] <= pre[b] < pre[a] + size[a], elementwise on
+        index tensors (or ints) a, b. Returns a bool GPU tensor."""
+        if self.pre is None or self.size is None:
+            raise ValueError("is_ancestor needs pre and size (forest_root(..., order=True))")
+        a = torch.as_tensor(a, device=self.pre.device).long()
+        b = torch.as_tensor(b, device=self.pre.device).long()
+        pa = self.pre[a].long() & 0xFFFFFFFF
+        pb = self.pre[b].long() & 0xFFFFFFFF
+        return (pa <= pb) & (pb < pa + (self.size[a].long() & 0xFFFFFFFF))
+
+
+def forest_root(edges, in_mst, order=True):
+    """Root the flagged forest on the device (ghs_forest_root_device, csrc/root.hip): every tree at
+    its smallest vertex (the convention of `forest_labels`), by an Euler tour and a splitter list
+    ranking, so a path costs what a star costs.
+    edges: a DeviceEdges with `u` present (a CSR-only list raises ValueError); in_mst: a uint8 / bool
+    GPU tensor of at least m flags (nonzero = in the forest), only read. More than min(m, n - 1) flags
+    raise GHSError (GHS_E_ARG); flags that close a cycle are reported as info["is_forest"] = False, and
+    the arrays are then unspecified.
+    Returns (rooted, info): rooted a RootedForest with .parent (0xffffffff for a root), .parent_eid
+    (the canonical id of the edge to the parent), .depth, .pre (a DFS preorder: trees in root order,
+    children in ascending id cyclically after the parent) and .size (subtree sizes), so that a is an
+    ancestor-or-self of b iff pre[a] <= pre[b] < pre[a] + size[a] (`rooted.is_ancestor`). order=False
+    leaves pre and size out (None). info: the fields of ghs_root_result_t as a dict: flagged_edges,
+    num_trees, max_depth, rounds, is_forest, ms_total. Runs on torch's current stream; a non-canonical
+    list raises GHSError (GHS_E_NONCANON)."""
+    if edges.u is None:
+        raise ValueError("forest_root needs the COO form (u present); a CSR-only list is not supported")
+    if not isinstance(in_mst, torch.Tensor) or in_mst.dim() != 1:
+        raise ValueError("in_mst: a one-dimensional GPU tensor of flags expected")
+    if in_mst.dtype == torch.bool:
+        in_mst = in_mst.view(torch.uint8)
+    if in_mst.dtype != torch.uint8:
+        raise ValueError(f"in_mst: uint8 or bool flags expected, got {in_mst.dtype}")
+    n, m = edges.n, edges.m
+    if in_mst.numel() < m:
+        raise ValueError(f"in_mst holds {in_mst.numel()} flags, the edge list {m} edges")
+    L = _native.load()
+    _native.require_gpu()
+    if m and (not in_mst.is_cuda or in_mst.device != edges.device):
+        raise ValueError("in_mst must be on the edge list's device")
+    if m and in_mst.stride(0) != 1:
+        in_mst = in_mst.contiguous()
+    with torch.cuda.device(edges.device):
+        res = _native.RootResult()
+        out = [torch.empty(n, dtype=torch.int32, device=edges.device) for _ in range(5 if order else 3)]
+        out += [None] * (5 - len(out))
+        ws_bytes = int(L.ghs_forest_root_workspace_bytes(n, m)) if m else 0
+        ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=edges.device)
+        _native.check(L.ghs_forest_root_device(n, m, _ptr(edges.u), _ptr(edges.v), _ptr(in_mst) if m else None,
+                                               *[_ptr(t) for t in out], _ptr(ws), ws_bytes, _stream(),
+                                               ctypes.byref(res)))
+    del ws
+    return RootedForest(*out), res.as_dict()
 
 
 class DeviceBatch:

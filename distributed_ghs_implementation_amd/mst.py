@@ -95,6 +95,25 @@ class MSTResult:
         return (out, info) if return_info else out
 
 
+    def rooted(self, return_info=False):
+        """The forest rooted at every tree's smallest vertex (ghs_forest_root_host, on the GPU): a dict
+        of numpy uint32 arrays of n entries: parent and parent_eid (0xffffffff for a root), depth,
+        pre (a DFS preorder: trees in root order, children in ascending id cyclically after the
+        parent) and size (subtree sizes), so that a is an ancestor-or-self of b iff
+        pre[a] <= pre[b] < pre[a] + size[a]. return_info=True: (arrays, the fields of
+        ghs_root_result_t as a dict)."""
+        g = self.graph
+        L = _native.load()
+        _native.require_gpu()
+        flags = np.ascontiguousarray(self.in_mst, dtype=np.uint8)
+        names = ("parent", "parent_eid", "depth", "pre", "size")
+        out = {k: np.empty(g.n, dtype=np.uint32) for k in names}
+        res = _native.RootResult()
+        _native.check(L.ghs_forest_root_host(g.n, g.m, g.u.ctypes.data, g.v.ctypes.data, flags.ctypes.data,
+                                             *[out[k].ctypes.data for k in names], ctypes.byref(res)))
+        return (out, res.as_dict()) if return_info else out
+
+
 def _weights_at_most(weights, t):
     """weights <= t as a mask; integer arrays are compared as integers, exactly at any magnitude."""
     import math

@@ -435,6 +435,81 @@ int ghs_forest_labels_host(uint32_t n, uint64_t m, const uint32_t *u, const uint
                            const uint8_t *in_mst, uint32_t mode, uint64_t param, uint32_t *labels,
                            ghs_labels_result_t *result);
 
+/* ---- rooted forest: parent, depth and preorder of every vertex (ABI 10 addition) ---------------
+ * The reference's nodes end a run with in_branch, the neighbour towards their fragment's core
+ * (ghs_implementation.py:63,212, ghs_implementation_mpi.py:57,309), and its REPORT / CHANGEROOT
+ * convergecasts walk those pointers; the flags this engine returns carry no orientation. This entry
+ * roots the flagged forest on the device, at any depth (a path costs what a star costs: nothing is
+ * level-synchronous). T = the edges with a nonzero flag byte, as everywhere else. Exact and
+ * deterministic: two calls give identical bytes.
+ *   root        the root of a tree is its smallest vertex (the convention of the labels call: label
+ *               order = root order); an isolated vertex is a root.
+ *   parent[v]   the neighbour of v on the T-path to its root; 0xffffffff for a root.
+ *   parent_eid[v]  the canonical edge id of {v, parent[v]}; 0xffffffff for a root.
+ *   depth[v]    the number of edges to the root.
+ *   size[v]     the number of vertices in v's subtree, v included.
+ *   pre[v]      a DFS preorder number, a permutation of 0..n-1. Trees take consecutive blocks of
+ *               numbers in order of their roots. Inside a tree the root gets the block's first number
+ *               and visits its children in ascending id. A vertex x entered from parent p visits its
+ *               children in ascending id cyclically, starting after p: first the children greater
+ *               than p, then those less than p. (The order the Euler tour gives: with every adjacency
+ *               sorted by neighbour id, succ(x -> y) is the arc after (y -> x) in y's cyclic
+ *               adjacency.) It is a genuine DFS preorder: a is an ancestor-or-self of b exactly when
+ *               pre[a] <= pre[b] < pre[a] + size[a], and every subtree is one contiguous range.
+ * d_pre and d_size may be NULL, independently (not written then).
+ * A T that closes a cycle is a result, not an error: GHS_OK with is_forest = 0 and flagged_edges exact;
+ * all other fields and the five arrays are then unspecified (written only in bounds; no loop depends
+ * on T being acyclic). More than min(m, n - 1) flagged edges cannot be a forest and do not fit the
+ * workspace: GHS_E_ARG ("more flags than a forest can hold") after the count, nothing else written.
+ * Method (csrc/root.hip): the flags are streamed 16 per lane (any byte alignment) and (u, v, eid) of
+ * the flagged edges gathered in eid order; a stable rocPRIM pairs sort by v gives the reverse arcs,
+ * so a vertex's reverse block then forward block is its adjacency in ascending neighbour id, with no
+ * atomics; the Euler successor permutation over the 2|T| arcs; a splitter list ranking (splitters: the
+ * first arc of every vertex that is the smallest within two hops + a hashed 1-in-64 sample; one lane walks each
+ * sublist; Wyllie doubling with min-carry on the circular list of splitters finds each tour's smallest
+ * vertex and breaks the tour at its first arc, a second doubling ranks the splitters; a second walk
+ * writes every arc's tour position); the earlier arc of a tree edge is its down arc (parent,
+ * parent_eid, size), and a scan of the down arcs in tour order gives depth and pre.
+ * rounds = the doubling rounds of both phases, each ended by a round that changes nothing:
+ * rounds <= 2 ceil(log2(2 |T|)) + 2 (DESIGN.md "Rooted forest" has the proof); GHS_E_ROUNDCAP past
+ * it is never expected. T is a forest iff every arc lies on a tour with a splitter and the number of
+ * roots (isolated vertices + smallest vertices of tours) is n - |T|.
+ * d_in_mst (m bytes, any alignment) is only read. Work is enqueued on `stream`; the call returns once
+ * *result and the arrays are final (4 host syncs + one per round).
+ * Workspace (ghs_forest_root_workspace_bytes, computed on the host, no GPU needed; C = min(m, n - 1)
+ * possible tree edges): 29 B per vertex (adjacency ranges 16, tree size 4, root prefix 8, a flag 1) + 24 B per
+ * possible tree edge (u, v, eid, sorted keys, permutation, inverse) + 84 B per possible arc (2 C: arc
+ * record 8, tour position 4, and per possible splitter its arc 4, length 4, predecessor 4, key 8, root
+ * 4, two 16-byte and two 8-byte doubling buffers) + 12 B per 64 arcs of splitter bits + the tile sums
+ * of the largest scan + rocPRIM's sort storage + 1 KiB of status.
+ * Errors, checked before any device work (so they hold on a host without GPU): result NULL,
+ * m >= 2^31, NULL or misaligned pointers (16 bytes for u / v / workspace, 4 for the five outputs):
+ * GHS_E_ARG; workspace_bytes short: GHS_E_NOMEM. n == 0: GHS_OK, nothing written. m == 0, n > 0: every
+ * vertex is a root (parent and parent_eid 0xffffffff, depth 0, pre[v] = v, size 1; only the output
+ * pointers are needed). A non-canonical list (ghs_check_canonical): GHS_E_NONCANON before any index is
+ * formed from it. */
+typedef struct ghs_root_result {   /* 48 bytes */
+  uint64_t flagged_edges;   /* |T| */
+  uint64_t num_trees;       /* roots written (isolated vertices included) */
+  uint64_t max_depth;
+  uint32_t rounds;          /* data-dependent launch rounds of the ranking */
+  uint32_t is_forest;       /* 1 iff T closes no cycle */
+  double   ms_total;        /* host wall time of the call */
+  uint64_t reserved;        /* 0 */
+} ghs_root_result_t;
+size_t ghs_forest_root_workspace_bytes(uint32_t n, uint64_t m);   /* host only, no GPU needed */
+int ghs_forest_root_device(uint32_t n, uint64_t m, const uint32_t *d_u, const uint32_t *d_v,
+                           const uint8_t *d_in_mst,
+                           uint32_t *d_parent, uint32_t *d_parent_eid, uint32_t *d_depth,
+                           uint32_t *d_pre /* may be NULL */, uint32_t *d_size /* may be NULL */,
+                           void *d_workspace, size_t workspace_bytes, void *stream,
+                           ghs_root_result_t *result);
+/* the same for host arrays (copy in, run, copy out on the default stream; pre and size may be NULL);
+ * the argument errors above except the alignments, then GHS_E_NODEVICE without a GPU */
+int ghs_forest_root_host(uint32_t n, uint64_t m, const uint32_t *u, const uint32_t *v, const uint8_t *in_mst,
+                         uint32_t *parent, uint32_t *parent_eid, uint32_t *depth, uint32_t *pre, uint32_t *size,
+                         ghs_root_result_t *result);
+
 /* device-side canonicity check: *ok = 1 iff u < v < n and (u, v) strictly ascending */
 int ghs_check_canonical(uint32_t n, uint64_t m, const uint32_t *d_u, const uint32_t *d_v, void *stream, int *ok);
 
