@@ -13,6 +13,8 @@ device.canonicalize_device; the forest's vertex labels (connected components, si
 weight or cluster count): device.forest_labels, DeviceMST.labels, MSTResult.labels, CLI --labels;
 the forest rooted (parent, parent edge, depth, DFS preorder, subtree size per vertex):
 device.forest_root, DeviceMST.rooted, MSTResult.rooted, CLI --rooted;
+path queries on it (heaviest edge between a and b = the minimax distance, lowest common ancestor,
+hop count): device.forest_paths, DeviceMST.paths, MSTResult.paths, CLI --paths / --pairs;
 multi-GPU: distributed.DistributedMST. Float, negative and 64-bit
 weights: rank-mapped by graph.canonicalize on the host, or on the device with rank_weights=True
 (minimum_spanning_forest_edges, DeviceEdges.from_raw, canonicalize_device; device.weight_ranks).

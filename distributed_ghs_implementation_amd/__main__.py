@@ -24,6 +24,12 @@
                    after the solve, write the forest rooted at every tree's smallest vertex: numpy
                    uint32 arrays parent, parent_eid (0xffffffff for a root), depth, pre (DFS preorder)
                    and size (subtree sizes), computed on the GPU
+    --paths OUT.npz --pairs PAIRS.npy
+                   after the solve, answer path queries on the forest on the GPU: PAIRS.npy is an
+                   integer array of shape (Q, 2); OUT.npz holds a, b, eid (the heaviest edge between
+                   a and b on the forest, 0xffffffff where there is none), weight (its weight: the
+                   minimax distance of a and b in the graph), lca and hops (0xffffffff for different
+                   components)
 
     --batch-dir ROOT
                    many small graphs in one launch: every immediate subdirectory of ROOT holding
@@ -128,6 +134,10 @@ def main(argv=None):
                     help="with --labels: keep forest edges of weight <= T (single linkage at distance T)")
     ap.add_argument("--rooted", type=str, default=None, metavar="OUT.npz",
                     help="write the rooted forest (parent, parent_eid, depth, pre, size: uint32) after the solve")
+    ap.add_argument("--paths", type=str, default=None, metavar="OUT.npz",
+                    help="write the path queries' answers (a, b, eid, weight, lca, hops) after the solve; needs --pairs")
+    ap.add_argument("--pairs", type=str, default=None, metavar="PAIRS.npy",
+                    help="with --paths: the vertex pairs to query, an integer array of shape (Q, 2)")
     ap.add_argument("--gpus", type=int, default=1, help="GPUs driven by this one process (RCCL clique)")
     ap.add_argument("--generator", choices=["rmat", "grid"], default=None, help="synthetic graph instead of a file")
     ap.add_argument("--scale", type=int, default=16, help="R-MAT scale (2^scale vertices) / grid side k")
@@ -137,6 +147,8 @@ def main(argv=None):
         ap.error("--clusters and --max-weight exclude each other")
     if (args.clusters is not None or args.max_weight is not None) and not args.labels:
         ap.error("--clusters / --max-weight need --labels OUT.npy")
+    if (args.paths is None) != (args.pairs is None):
+        ap.error("--paths OUT.npz and --pairs PAIRS.npy go together")
     if args.batch_dir is not None:
         return run_batch_dir(args)
 
@@ -236,6 +248,20 @@ def main(argv=None):
         if not args.quiet:
             print(f"Rooted forest: {rinfo['num_trees']} trees, max depth {rinfo['max_depth']}")
             print(f"Rooted forest saved to: {args.rooted}")
+    if args.paths:
+        import numpy as np
+
+        from .mst import MSTResult
+        pairs = np.load(args.pairs)
+        if pairs.ndim != 2 or pairs.shape[1] != 2 or pairs.dtype.kind not in "iu":
+            raise ValueError(f"{args.pairs}: an integer array of shape (Q, 2) expected, got {pairs.dtype} {pairs.shape}")
+        ans, pinfo = MSTResult(g, np.asarray(flags), 0, rounds, [], ms).paths(pairs[:, 0], pairs[:, 1], return_info=True)
+        np.savez(args.paths, a=pairs[:, 0], b=pairs[:, 1], eid=ans["eid"], weight=ans["weight"], lca=ans["lca"],
+                 hops=ans["hops"])
+        if not args.quiet:
+            heaviest = ans["weight"][ans["has_edge"]].max() if ans["has_edge"].any() else "none"
+            print(f"Path queries: {len(pairs)} pairs, {int(ans['connected'].sum())} connected, max bottleneck {heaviest}")
+            print(f"Path answers saved to: {args.paths}")
     status = 0
     if args.check:
         from .verify import format_report, verify_forest

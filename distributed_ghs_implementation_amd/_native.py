@@ -63,6 +63,8 @@ EXPORTED_SYMBOLS = (
     "ghs_verify_workspace_bytes", "ghs_verify_msf_device",
     "ghs_forest_labels_workspace_bytes", "ghs_forest_labels_device", "ghs_forest_labels_host",
     "ghs_forest_root_workspace_bytes", "ghs_forest_root_device", "ghs_forest_root_host",
+    "ghs_forest_paths_index_bytes", "ghs_forest_paths_create", "ghs_forest_paths_query", "ghs_forest_paths_destroy",
+    "ghs_forest_paths_host",
 )
 
 
@@ -211,6 +213,34 @@ class RootResult(ctypes.Structure):
         d = {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
         d["is_forest"] = bool(d["is_forest"])
         return d
+
+
+class PathsResult(ctypes.Structure):
+    """ghs_paths_result_t: what ghs_forest_paths_create built."""
+    _fields_ = [
+        ("levels", ctypes.c_uint64),
+        ("max_depth", ctypes.c_uint64),
+        ("num_trees", ctypes.c_uint64),
+        ("index_bytes", ctypes.c_uint64),
+        ("ms_total", ctypes.c_double),
+        ("reserved", ctypes.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class PathsQueryResult(ctypes.Structure):
+    """ghs_paths_query_result_t: one ghs_forest_paths_query / ghs_forest_paths_host call."""
+    _fields_ = [
+        ("queries", ctypes.c_uint64),
+        ("connected", ctypes.c_uint64),
+        ("ms_total", ctypes.c_double),
+        ("reserved", ctypes.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
 # the same layout as a numpy structured dtype (a device buffer of results viewed on the host)
@@ -411,6 +441,12 @@ def load():
             "ghs_forest_root_workspace_bytes": (sz, [u32, u64]),
             "ghs_forest_root_device": (i32, [u32, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, P(RootResult)]),
             "ghs_forest_root_host": (i32, [u32, u64, vp, vp, vp, vp, vp, vp, vp, vp, P(RootResult)]),
+            # ABI 10 addition: path queries on the rooted forest (bottleneck edge, LCA, hop count)
+            "ghs_forest_paths_index_bytes": (sz, [u32, u64]),
+            "ghs_forest_paths_create": (i32, [u32, u64, vp, vp, vp, vp, vp, vp, u64, vp, sz, vp, P(PathsResult), P(vp)]),
+            "ghs_forest_paths_query": (i32, [vp, u64, vp, vp, vp, vp, vp, vp, P(PathsQueryResult)]),
+            "ghs_forest_paths_destroy": (i32, [vp]),
+            "ghs_forest_paths_host": (i32, [u32, u64, vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, P(PathsQueryResult)]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(L, name)

@@ -125,3 +125,64 @@ extern "C" int ghs_forest_root_host(uint32_t n, uint64_t m, const uint32_t *u, c
     if (h_out[k]) GHS_HIP_CHECK(hipMemcpy(h_out[k], d_out[k], (size_t)n * 4, hipMemcpyDeviceToHost));
   return GHS_OK;
 }
+
+// Host-buffer form of the path queries (what a reference user asks of a result by walking in_branch,
+// ghs_implementation.py:235-387): copy in, root the flags, build the jump-pointer index, query, copy out.
+extern "C" int ghs_forest_paths_host(uint32_t n, uint64_t m, const uint32_t *u, const uint32_t *v, const uint32_t *w,
+                                     const uint8_t *in_mst, uint64_t q, const uint32_t *a, const uint32_t *b,
+                                     uint64_t *key, uint32_t *lca, uint32_t *hops, ghs_paths_query_result_t *result) {
+  if (!result) GHS_FAIL(GHS_E_ARG, "result is NULL");
+  *result = ghs_paths_query_result_t{};
+  if (m >= (1ull << 31)) GHS_FAIL(GHS_E_ARG, "m must be < 2^31");
+  if (q >= (1ull << 32)) GHS_FAIL(GHS_E_ARG, "q must be < 2^32");
+  if ((m && (!u || !v || !w || !in_mst)) || (q && (!a || !b))) GHS_FAIL(GHS_E_ARG, "NULL host pointer");
+  if (q == 0) return GHS_OK;
+  result->queries = q;
+  if (n == 0) GHS_FAIL(GHS_E_ARG, "vertex id out of range");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) GHS_FAIL(GHS_E_NODEVICE, "no HIP device");
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  hipStream_t st = nullptr;
+  // stage 1: the edges, the flags, the rooted arrays, the rooting's workspace
+  const size_t ws = m ? ghs_forest_root_workspace_bytes(n, m) : 0;
+  const size_t nb = al((size_t)n * 4);
+  const size_t off_u = 0, off_v = off_u + al(m * 4), off_w = off_v + al(m * 4), off_f = off_w + al(m * 4),
+               off_o = off_f + al(m ? m : 1), off_ws = off_o + 3 * nb, total = off_ws + al(ws ? ws : 1);
+  DevBuf buf;
+  GHS_HIP_CHECK(hipMalloc(&buf.p, total));
+  char *d = (char *)buf.p;
+  if (m) {
+    GHS_HIP_CHECK(hipMemcpyAsync(d + off_u, u, m * 4, hipMemcpyHostToDevice, st));
+    GHS_HIP_CHECK(hipMemcpyAsync(d + off_v, v, m * 4, hipMemcpyHostToDevice, st));
+    GHS_HIP_CHECK(hipMemcpyAsync(d + off_w, w, m * 4, hipMemcpyHostToDevice, st));
+    GHS_HIP_CHECK(hipMemcpyAsync(d + off_f, in_mst, m, hipMemcpyHostToDevice, st));
+  }
+  uint32_t *d_par = (uint32_t *)(d + off_o), *d_peid = (uint32_t *)(d + off_o + nb), *d_dep = (uint32_t *)(d + off_o + 2 * nb);
+  ghs_root_result_t rr;
+  int rc = ghs_forest_root_device(n, m, (uint32_t *)(d + off_u), (uint32_t *)(d + off_v), (uint8_t *)(d + off_f), d_par,
+                                  d_peid, d_dep, nullptr, nullptr, d + off_ws, ws, st, &rr);
+  if (rc) return rc;
+  if (!rr.is_forest) GHS_FAIL(GHS_E_ARG, "flags are not a forest");
+  // stage 2: the index, the pairs, the answers
+  const size_t ib = ghs_forest_paths_index_bytes(n, rr.max_depth);
+  const size_t qb = al(q * 4);
+  const size_t off_a = al(ib), off_b = off_a + qb, off_k = off_b + qb, off_l = off_k + al(q * 8), off_h = off_l + qb;
+  DevBuf ibuf;
+  GHS_HIP_CHECK(hipMalloc(&ibuf.p, off_h + qb));
+  char *x = (char *)ibuf.p;
+  GHS_HIP_CHECK(hipMemcpyAsync(x + off_a, a, q * 4, hipMemcpyHostToDevice, st));
+  GHS_HIP_CHECK(hipMemcpyAsync(x + off_b, b, q * 4, hipMemcpyHostToDevice, st));
+  ghs_paths_result_t pr;
+  ghs_paths_t *h = nullptr;
+  rc = ghs_forest_paths_create(n, m, (uint32_t *)(d + off_u), (uint32_t *)(d + off_v), (uint32_t *)(d + off_w), d_par, d_peid,
+                               d_dep, rr.max_depth, x, ib, st, &pr, &h);
+  if (rc) return rc;
+  rc = ghs_forest_paths_query(h, q, (uint32_t *)(x + off_a), (uint32_t *)(x + off_b), key ? (uint64_t *)(x + off_k) : nullptr,
+                              lca ? (uint32_t *)(x + off_l) : nullptr, hops ? (uint32_t *)(x + off_h) : nullptr, st, result);
+  (void)ghs_forest_paths_destroy(h);
+  if (rc) return rc;
+  if (key) GHS_HIP_CHECK(hipMemcpy(key, x + off_k, q * 8, hipMemcpyDeviceToHost));
+  if (lca) GHS_HIP_CHECK(hipMemcpy(lca, x + off_l, q * 4, hipMemcpyDeviceToHost));
+  if (hops) GHS_HIP_CHECK(hipMemcpy(hops, x + off_h, q * 4, hipMemcpyDeviceToHost));
+  return GHS_OK;
+}

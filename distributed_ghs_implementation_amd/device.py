@@ -417,6 +417,11 @@ class DeviceMST:
         its smallest vertex."""
         return forest_root(self.edges, self.in_mst, order=order)
 
+    def paths(self):
+        """`forest_paths` of the engine's own flags (after `run()`): a PathIndex answering bottleneck
+        edge / LCA / hop-count queries on the MSF."""
+        return forest_paths(self.edges, self.in_mst)
+
 
 def verify_msf(edges, in_mst):
     """Is `in_mst` THE minimum spanning forest of `edges`? Checked on the device, exactly, without a
@@ -633,6 +638,155 @@ def forest_root(edges, in_mst, order=True):
                                                ctypes.byref(res)))
     del ws
     return RootedForest(*out), res.as_dict()
+
+
+class PathAnswers:
+    """What `PathIndex.query` returns, one entry per pair, on the device.
+    key: int64 holding the uint64 w << 32 | eid of the heaviest edge (largest key) on the forest path;
+    all ones (-1) when a == b or the ends are in different trees. eid / w: its two halves as int32
+    holding uint32 bit patterns (-1 where there is no edge). lca, hops: int32 holding uint32; -1 where
+    the ends are in different trees (lca = a and hops = 0 when a == b). A field left out of the query
+    is None. info: the fields of ghs_paths_query_result_t as a dict (queries, connected, ms_total)."""
+
+    def __init__(self, key, lca, hops, info=None):
+        self.key, self.lca, self.hops, self.info = key, lca, hops, info
+
+    def _need(self, name):
+        t = getattr(self, name)
+        if t is None:
+            raise ValueError(f"the query was made without {name}")
+        return t
+
+    @property
+    def eid(self):
+        return self._need("key").view(torch.int32).view(-1, 2)[:, 0]
+
+    @property
+    def w(self):
+        return self._need("key").view(torch.int32).view(-1, 2)[:, 1]
+
+    @property
+    def has_edge(self):
+        """bool: the path has an edge (the ends are distinct and in one tree)."""
+        return self._need("key") != -1
+
+    @property
+    def connected(self):
+        """bool: the ends are in one tree (a == b included)."""
+        return self._need("lca") != -1
+
+    def weights(self, edges):
+        """The bottleneck weights in the caller's own units: (values, has_edge). With rank-mapped
+        weights (`edges.weights` set) values = edges.weights[eid], of that tensor's dtype; otherwise the
+        engine's uint32 weights as int64. Where has_edge is False the value is NaN for float weights
+        and 0 for integer ones."""
+        mask = self.has_edge
+        eid = torch.where(mask, self.eid.to(torch.int64) & 0xFFFFFFFF, torch.zeros_like(self.key))
+        if edges.weights is None:
+            vals = self.w.to(torch.int64) & 0xFFFFFFFF
+            return torch.where(mask, vals, torch.zeros_like(vals)), mask
+        wt = edges.weights
+        if wt.numel() == 0:
+            return torch.zeros(eid.numel(), dtype=wt.dtype, device=eid.device), mask
+        vals = wt[eid]
+        none = float("nan") if wt.dtype.is_floating_point else 0
+        return torch.where(mask, vals, torch.full_like(vals, none)), mask
+
+
+class PathIndex:
+    """The jump-pointer index of a rooted forest (`forest_paths`; ghs_forest_paths_create). Keeps the
+    index tensor alive; `close()` (or deletion) destroys the native handle. One query at a time per
+    index: the calls' status block lives in the index."""
+
+    def __init__(self, handle, index, n, device):
+        self._h, self._index, self.n, self.device = handle, index, int(n), device
+
+    def query(self, a, b, key=True, lca=True, hops=True):
+        """a, b: int32 (uint32 bit patterns) or int64 GPU tensors of equal length, or ints. Returns a
+        PathAnswers; key / lca / hops = False leaves that output out. An id >= n raises GHSError
+        (GHS_E_ARG), a value outside [0, 2^32) ValueError. Runs on torch's current stream."""
+        if not self._h:
+            raise ValueError("the index is closed")
+        ta = torch.as_tensor(a, device=self.device).reshape(-1) if not isinstance(a, torch.Tensor) else a
+        tb = torch.as_tensor(b, device=self.device).reshape(-1) if not isinstance(b, torch.Tensor) else b
+        for name, t in (("a", ta), ("b", tb)):
+            if t.dim() != 1 or t.device != self.device:
+                raise ValueError(f"{name}: a one-dimensional tensor on the index's device (or an int) expected")
+        if ta.numel() != tb.numel():
+            raise ValueError("a and b must have equal length")
+        ta, tb = _as_u32_tensor(ta, "a"), _as_u32_tensor(tb, "b")
+        q = int(ta.numel())
+        if q >= (1 << 32):
+            raise ValueError("at most 2^32 - 1 pairs")
+        with torch.cuda.device(self.device):
+            okey = torch.empty(q, dtype=torch.int64, device=self.device) if key else None
+            olca = torch.empty(q, dtype=torch.int32, device=self.device) if lca else None
+            ohops = torch.empty(q, dtype=torch.int32, device=self.device) if hops else None
+            res = _native.PathsQueryResult()
+            _native.check(_native.load().ghs_forest_paths_query(self._h, q, _ptr(ta), _ptr(tb), _ptr(okey), _ptr(olca),
+                                                                _ptr(ohops), _stream(), ctypes.byref(res)))
+        return PathAnswers(okey, olca, ohops, res.as_dict())
+
+    def close(self):
+        if self._h:
+            _native.load().ghs_forest_paths_destroy(self._h)
+            self._h = None
+        self._index = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def forest_paths(edges, in_mst=None, rooted=None, max_depth=None):
+    """Index the flagged forest for path queries, on the device (ghs_forest_paths_create,
+    csrc/paths.hip): jump pointers over parent / parent_eid / depth, K = max(1, bit_length(max_depth))
+    levels of n 16-byte nodes. `PathIndex.query(a, b)` then gives, per pair, the heaviest edge of the
+    forest path (with the engine's MSF: the minimax distance in the graph, the edge a new edge (a, b)
+    would displace, the single-linkage merge height), the lowest common ancestor and the hop count.
+    Give the flags (in_mst: a uint8 / bool GPU tensor of at least m flags, only read; rooted here with
+    `forest_root(order=False)`; flags that close a cycle raise ValueError) or a RootedForest together
+    with its max_depth (an upper bound of the depths: info["max_depth"] of `forest_root`). The arrays
+    are validated on the device; anything that is not a rooted forest of this edge list raises
+    GHSError (GHS_E_ARG). edges: a DeviceEdges with `u` present.
+    Returns (index, info): info the fields of ghs_paths_result_t as a dict: levels, max_depth,
+    num_trees, index_bytes, ms_total. Runs on torch's current stream."""
+    if edges.u is None:
+        raise ValueError("forest_paths needs the COO form (u present); a CSR-only list is not supported")
+    if (in_mst is None) == (rooted is None):
+        raise ValueError("give in_mst or rooted (with max_depth), not both and not neither")
+    if rooted is not None and max_depth is None:
+        raise ValueError("a RootedForest needs its max_depth (info['max_depth'] of forest_root)")
+    n, m = edges.n, edges.m
+    if rooted is None:
+        rooted, rinfo = forest_root(edges, in_mst, order=False)
+        if not rinfo["is_forest"]:
+            raise ValueError("in_mst is not a forest (the flags close a cycle)")
+        max_depth = rinfo["max_depth"]
+    max_depth = int(max_depth)
+    if max_depth < 0:
+        raise ValueError("max_depth must be >= 0")
+    for name in ("parent", "parent_eid", "depth"):
+        t = getattr(rooted, name)
+        if not (isinstance(t, torch.Tensor) and t.dim() == 1 and t.dtype == torch.int32 and t.numel() >= n):
+            raise ValueError(f"rooted.{name}: an int32 tensor of n entries expected")
+    L = _native.load()
+    _native.require_gpu()
+    dev = edges.device
+    par, peid, dep = (getattr(rooted, k).contiguous() for k in ("parent", "parent_eid", "depth"))
+    if n and not all(t.is_cuda and t.device == dev for t in (par, peid, dep)):
+        raise ValueError("the rooted arrays must be on the edge list's device")
+    with torch.cuda.device(dev):
+        ib = int(L.ghs_forest_paths_index_bytes(n, max_depth))
+        index = torch.empty(max(ib, 256), dtype=torch.uint8, device=dev)
+        res = _native.PathsResult()
+        h = ctypes.c_void_p(0)
+        _native.check(L.ghs_forest_paths_create(n, m, _ptr(edges.u), _ptr(edges.v), _ptr(edges.w), _ptr(par), _ptr(peid),
+                                                _ptr(dep), max_depth, _ptr(index), ib, _stream(), ctypes.byref(res),
+                                                ctypes.byref(h)))
+    return PathIndex(h, index, n, dev), res.as_dict()
 
 
 class DeviceBatch:

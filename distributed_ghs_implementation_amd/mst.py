@@ -113,6 +113,56 @@ class MSTResult:
                                              *[out[k].ctypes.data for k in names], ctypes.byref(res)))
         return (out, res.as_dict()) if return_info else out
 
+    def paths(self, a, b, return_info=False):
+        """What lies between a[i] and b[i] on the forest (ghs_forest_paths_host, on the GPU: the flags
+        rooted, a jump-pointer index, one batched query). a, b: integer arrays of equal length (or
+        ints) with ids in [0, n). Returns a dict of numpy arrays, one entry per pair:
+          eid       uint32, the canonical id of the heaviest edge (largest (w, eid)) of the path;
+                    0xffffffff where there is none (a == b, or different trees)
+          weight    that edge's weight in the graph's own weights: for integer engine weights int64
+                    with -1 where there is no edge; for a rank-mapped graph the dtype of graph.weights,
+                    NaN (floats) or 0 (integers) where there is no edge
+          has_edge  bool, eid != 0xffffffff
+          lca       uint32, the lowest common ancestor with every tree rooted at its smallest vertex
+                    (a itself when a == b); 0xffffffff for different trees
+          hops      uint32, the number of edges of the path; 0xffffffff for different trees
+          connected bool, a and b are in one tree
+        With the engine's forest the weight is the minimax distance between a and b in the graph.
+        An id outside [0, n) raises ValueError. return_info=True: (dict, the fields of
+        ghs_paths_query_result_t as a dict)."""
+        g = self.graph
+        qa, qb = np.atleast_1d(np.asarray(a)), np.atleast_1d(np.asarray(b))
+        if qa.ndim != 1 or qa.shape != qb.shape or qa.dtype.kind not in "iu" or qb.dtype.kind not in "iu":
+            raise ValueError("a, b: one-dimensional integer arrays of equal length (or ints) expected")
+        q = len(qa)
+        if q and (int(qa.min()) < 0 or int(qb.min()) < 0 or int(qa.max()) >= g.n or int(qb.max()) >= g.n):
+            raise ValueError(f"a, b: vertex ids must be in [0, {g.n})")
+        qa, qb = np.ascontiguousarray(qa, dtype=np.uint32), np.ascontiguousarray(qb, dtype=np.uint32)
+        L = _native.load()
+        if q:
+            _native.require_gpu()
+        flags = np.ascontiguousarray(self.in_mst, dtype=np.uint8)
+        key = np.empty(q, dtype=np.uint64)
+        lca = np.empty(q, dtype=np.uint32)
+        hops = np.empty(q, dtype=np.uint32)
+        res = _native.PathsQueryResult()
+        _native.check(L.ghs_forest_paths_host(g.n, g.m, g.u.ctypes.data, g.v.ctypes.data, g.w.ctypes.data,
+                                              flags.ctypes.data, q, qa.ctypes.data, qb.ctypes.data, key.ctypes.data,
+                                              lca.ctypes.data, hops.ctypes.data, ctypes.byref(res)))
+        has_edge = key != np.uint64((1 << 64) - 1)
+        eid = (key & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+        at = np.where(has_edge, eid, 0).astype(np.int64)
+        if g.weights is None:
+            weight = np.where(has_edge, (key >> np.uint64(32)).astype(np.int64), -1)
+        elif g.m == 0:
+            weight = np.zeros(q, dtype=g.weights.dtype)
+        else:
+            none = np.nan if g.weights.dtype.kind == "f" else 0
+            weight = np.where(has_edge, g.weights[at], g.weights.dtype.type(none))
+        out = {"eid": eid, "weight": weight, "has_edge": has_edge, "lca": lca, "hops": hops,
+               "connected": lca != np.uint32(0xFFFFFFFF)}
+        return (out, res.as_dict()) if return_info else out
+
 
 def _weights_at_most(weights, t):
     """weights <= t as a mask; integer arrays are compared as integers, exactly at any magnitude."""

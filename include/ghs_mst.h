@@ -510,6 +510,88 @@ int ghs_forest_root_host(uint32_t n, uint64_t m, const uint32_t *u, const uint32
                          uint32_t *parent, uint32_t *parent_eid, uint32_t *depth, uint32_t *pre, uint32_t *size,
                          ghs_root_result_t *result);
 
+/* ---- path queries: what lies between a and b? (ABI 10 addition) ---------------------------------
+ * The reference's nodes answer questions about the tree by walking in_branch (the REPORT / CHANGEROOT
+ * convergecasts, ghs_implementation.py:235-387). These calls are the device form of that walk over
+ * the arrays ghs_forest_root_device writes, in O(log depth) dependent loads per query at any depth.
+ * For a pair (a, b):
+ *   key    the largest key w << 32 | eid among the edges of the forest path a .. b: the bottleneck
+ *          (minimax) edge. With the engine's MSF it is the minimax distance in the graph itself, the
+ *          edge a new edge (a, b, w) would displace from the MSF, and the single-linkage merge height
+ *          of a and b. UINT64_MAX when a == b (no edge) or when a and b are in different trees.
+ *   lca    the lowest common ancestor under the rooting given; a itself when a == b; 0xffffffff when a
+ *          and b are in different trees.
+ *   hops   the number of edges on the path, depth[a] + depth[b] - 2 depth[lca]; 0 when a == b;
+ *          0xffffffff when a and b are in different trees.
+ * Exact and deterministic: two calls give identical bytes.
+ * Index (ghs_forest_paths_create, csrc/paths.hip): K = max(1, bit_length(max_depth)) levels of n
+ * 16-byte nodes {uint64 key, uint32 up, uint32 aux}. Level 0: up = parent (the vertex itself for a
+ * root), key = w[parent_eid] << 32 | parent_eid (0 for a root), aux = depth. Level k: up_k[v] =
+ * up_{k-1}[up_{k-1}[v]], key_k[v] = max(key_{k-1}[v], key_{k-1}[up_{k-1}[v]]), aux = depth: K - 1
+ * stream-ordered launches, no host sync between them. A root points at itself with key 0, so a jump
+ * past a root is harmless. Key 0 is also the key of edge 0 with weight 0: a == b is decided before
+ * any key is looked at. The index keeps no reference to the caller's arrays: u, v, w, parent,
+ * parent_eid and depth may be released after create.
+ * The level-0 pass validates parent / parent_eid / depth, which become gather indices. Every vertex v
+ * is a root (parent == parent_eid == 0xffffffff and depth 0) or has parent < n, parent_eid < m,
+ * {u[e], v[e]} == {v, parent[v]}, depth[v] == depth[parent[v]] + 1 and depth[v] <= max_depth. Depth
+ * falls by one along every parent pointer, so what passes is acyclic and no later loop depends on
+ * trust. Anything else: GHS_E_ARG ("not a rooted forest") after the one host sync of the call, no
+ * handle; nothing is read or written out of bounds. max_depth is an upper bound of the depths (the
+ * max_depth of ghs_root_result_t); result->max_depth is the largest depth found.
+ * Memory: ghs_forest_paths_index_bytes(n, max_depth) = 16 K n rounded up to 256, + 256 bytes of status
+ * (computed on the host, no GPU needed), caller-owned, to be kept alive and unchanged until destroy.
+ * The handle is a small host object. The status block lives in the index, so one query at a time per
+ * handle; queries on different handles, or create on different indexes, may run concurrently.
+ * Query (ghs_forest_paths_query): q pairs d_a[i], d_b[i] -> d_key[i], d_lca[i], d_hops[i]; each output
+ * pointer may be NULL, independently (not written then). 4 queries per lane advance together: both
+ * level-0 nodes give the depths, the deeper end is lifted by the set bits of the depth difference,
+ * then levels bit_length(common depth) - 1 .. 1 are tried from the top (both ends jump where their
+ * targets differ) and one or two level-0 steps finish; hops comes from the jump counts. Work is
+ * enqueued on `stream`; the call returns once the outputs and *result are final (one host sync).
+ * connected counts the pairs with an lca (a == b included). An id >= n anywhere in d_a / d_b:
+ * GHS_E_ARG ("vertex id out of range") after the sync; the outputs are then unspecified and nothing
+ * was indexed out of range (the rule of ghs_canonicalize_device).
+ * Errors, checked before any device work (so they hold on a host without GPU): result, out or handle
+ * NULL, m >= 2^31, max_depth >= n (n > 0), q >= 2^32, NULL or misaligned pointers (16 bytes for u / v /
+ * w / index, 4 for parent / parent_eid / depth / a / b / lca / hops, 8 for key): GHS_E_ARG;
+ * index_bytes short: GHS_E_NOMEM. q == 0: GHS_OK, no device work. n == 0: create succeeds with 0
+ * trees and no device work (all pointers may be NULL); a query with q > 0 on it is GHS_E_ARG (every id
+ * is out of range). m == 0: every vertex must be a root; d_u / d_v / d_w may be NULL.
+ * ghs_forest_paths_destroy frees the handle only (NULL is accepted). */
+typedef struct ghs_paths ghs_paths_t;            /* host handle over caller-owned device memory */
+typedef struct ghs_paths_result {   /* 48 bytes */
+  uint64_t levels;          /* K */
+  uint64_t max_depth;       /* the largest depth found (<= the bound given) */
+  uint64_t num_trees;       /* roots */
+  uint64_t index_bytes;     /* ghs_forest_paths_index_bytes(n, max_depth) */
+  double   ms_total;        /* host wall time of the call */
+  uint64_t reserved;        /* 0 */
+} ghs_paths_result_t;
+typedef struct ghs_paths_query_result {   /* 32 bytes */
+  uint64_t queries;         /* q */
+  uint64_t connected;       /* pairs in one tree (a == b included) */
+  double   ms_total;        /* host wall time of the call */
+  uint64_t reserved;        /* 0 */
+} ghs_paths_query_result_t;
+size_t ghs_forest_paths_index_bytes(uint32_t n, uint64_t max_depth);          /* host only, no GPU needed */
+int ghs_forest_paths_create(uint32_t n, uint64_t m, const uint32_t *d_u, const uint32_t *d_v, const uint32_t *d_w,
+                            const uint32_t *d_parent, const uint32_t *d_parent_eid, const uint32_t *d_depth,
+                            uint64_t max_depth, void *d_index, size_t index_bytes, void *stream,
+                            ghs_paths_result_t *result, ghs_paths_t **out);
+int ghs_forest_paths_query(ghs_paths_t *h, uint64_t q, const uint32_t *d_a, const uint32_t *d_b,
+                           uint64_t *d_key /* may be NULL */, uint32_t *d_lca /* may be NULL */,
+                           uint32_t *d_hops /* may be NULL */, void *stream, ghs_paths_query_result_t *result);
+int ghs_forest_paths_destroy(ghs_paths_t *h);
+/* the same for host arrays and flags: copy in, root the flags (ghs_forest_root_device without pre and
+ * size), build the index, run the q queries, copy out; key, lca and hops may be NULL. The argument
+ * errors above except the alignments (and NULL u / v / w / in_mst with m > 0, NULL a / b with q > 0),
+ * then GHS_E_NODEVICE without a GPU. q == 0: GHS_OK, no device work. Flags that close a cycle:
+ * GHS_E_ARG ("flags are not a forest"). */
+int ghs_forest_paths_host(uint32_t n, uint64_t m, const uint32_t *u, const uint32_t *v, const uint32_t *w,
+                          const uint8_t *in_mst, uint64_t q, const uint32_t *a, const uint32_t *b,
+                          uint64_t *key, uint32_t *lca, uint32_t *hops, ghs_paths_query_result_t *result);
+
 /* device-side canonicity check: *ok = 1 iff u < v < n and (u, v) strictly ascending */
 int ghs_check_canonical(uint32_t n, uint64_t m, const uint32_t *d_u, const uint32_t *d_v, void *stream, int *ok);
 
