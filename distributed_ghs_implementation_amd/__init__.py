@@ -15,6 +15,9 @@ the forest rooted (parent, parent edge, depth, DFS preorder, subtree size per ve
 device.forest_root, DeviceMST.rooted, MSTResult.rooted, CLI --rooted;
 path queries on it (heaviest edge between a and b = the minimax distance, lowest common ancestor,
 hop count): device.forest_paths, DeviceMST.paths, MSTResult.paths, CLI --paths / --pairs;
+replacement edges (what takes a forest edge's place when it fails, the bridges, the best swap):
+device.forest_replacements, PathIndex.replacements, DeviceMST.replacements, MSTResult.replacements,
+CLI --replacements;
 multi-GPU: distributed.DistributedMST. Float, negative and 64-bit
 weights: rank-mapped by graph.canonicalize on the host, or on the device with rank_weights=True
 (minimum_spanning_forest_edges, DeviceEdges.from_raw, canonicalize_device; device.weight_ranks).

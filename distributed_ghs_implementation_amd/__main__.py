@@ -30,6 +30,13 @@
                    a and b on the forest, 0xffffffff where there is none), weight (its weight: the
                    minimax distance of a and b in the graph), lca and hops (0xffffffff for different
                    components)
+    --replacements OUT.npz
+                   after the solve, what takes each forest edge's place when it fails, on the GPU:
+                   eid_by_edge (uint32 per canonical edge: the lightest edge that reconnects the two
+                   halves, 0xffffffff for a bridge and for non-forest edges), key (uint64 per vertex:
+                   the replacement's w << 32 | eid of the edge to its parent in the rooted forest), and
+                   the counts tree_edges, covering_edges, cross_edges, bridges, improving, best_delta,
+                   best_out_eid, best_in_eid
 
     --batch-dir ROOT
                    many small graphs in one launch: every immediate subdirectory of ROOT holding
@@ -138,6 +145,8 @@ def main(argv=None):
                     help="write the path queries' answers (a, b, eid, weight, lca, hops) after the solve; needs --pairs")
     ap.add_argument("--pairs", type=str, default=None, metavar="PAIRS.npy",
                     help="with --paths: the vertex pairs to query, an integer array of shape (Q, 2)")
+    ap.add_argument("--replacements", type=str, default=None, metavar="OUT.npz",
+                    help="write every forest edge's replacement (eid_by_edge, key) and the bridge / best-swap counts")
     ap.add_argument("--gpus", type=int, default=1, help="GPUs driven by this one process (RCCL clique)")
     ap.add_argument("--generator", choices=["rmat", "grid"], default=None, help="synthetic graph instead of a file")
     ap.add_argument("--scale", type=int, default=16, help="R-MAT scale (2^scale vertices) / grid side k")
@@ -262,6 +271,18 @@ def main(argv=None):
             heaviest = ans["weight"][ans["has_edge"]].max() if ans["has_edge"].any() else "none"
             print(f"Path queries: {len(pairs)} pairs, {int(ans['connected'].sum())} connected, max bottleneck {heaviest}")
             print(f"Path answers saved to: {args.paths}")
+    if args.replacements:
+        import numpy as np
+
+        from .mst import MSTResult
+        rep, pinfo = MSTResult(g, np.asarray(flags), 0, rounds, [], ms).replacements(return_info=True, per_vertex=True)
+        counts = {k: np.asarray(v) for k, v in pinfo.items() if k != "ms_total"}
+        np.savez(args.replacements, eid_by_edge=rep["eid"], key=rep["key"], **counts)
+        if not args.quiet:
+            swap = (f"best swap {pinfo['best_out_eid']} -> {pinfo['best_in_eid']} ({pinfo['best_delta']:+d})"
+                    if pinfo["best_out_eid"] != 0xFFFFFFFF else "no swap")
+            print(f"Replacements: {pinfo['tree_edges']} forest edges, {pinfo['bridges']} bridges, {swap}")
+            print(f"Replacements saved to: {args.replacements}")
     status = 0
     if args.check:
         from .verify import format_report, verify_forest

@@ -64,7 +64,9 @@ EXPORTED_SYMBOLS = (
     "ghs_forest_labels_workspace_bytes", "ghs_forest_labels_device", "ghs_forest_labels_host",
     "ghs_forest_root_workspace_bytes", "ghs_forest_root_device", "ghs_forest_root_host",
     "ghs_forest_paths_index_bytes", "ghs_forest_paths_create", "ghs_forest_paths_query", "ghs_forest_paths_destroy",
-    "ghs_forest_paths_host",
+    "ghs_forest_paths_host", "ghs_forest_paths_info",
+    "ghs_forest_replace_workspace_bytes", "ghs_forest_replace_device", "ghs_forest_replace_host",
+    "ghs_forest_replace_phases",
 )
 
 
@@ -235,6 +237,38 @@ class PathsQueryResult(ctypes.Structure):
     _fields_ = [
         ("queries", ctypes.c_uint64),
         ("connected", ctypes.c_uint64),
+        ("ms_total", ctypes.c_double),
+        ("reserved", ctypes.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class PathsInfo(ctypes.Structure):
+    """ghs_paths_info_t: what a live ghs_paths_t indexes (ghs_forest_paths_info)."""
+    _fields_ = [
+        ("n", ctypes.c_uint64),
+        ("levels", ctypes.c_uint64),
+        ("max_depth", ctypes.c_uint64),
+        ("d_index", ctypes.c_void_p),
+    ]
+
+    def as_dict(self):
+        return {"n": self.n, "levels": self.levels, "max_depth": self.max_depth, "d_index": self.d_index or 0}
+
+
+class ReplaceResult(ctypes.Structure):
+    """ghs_replace_result_t: one ghs_forest_replace_device / ghs_forest_replace_host call."""
+    _fields_ = [
+        ("tree_edges", ctypes.c_uint64),
+        ("covering_edges", ctypes.c_uint64),
+        ("cross_edges", ctypes.c_uint64),
+        ("bridges", ctypes.c_uint32),
+        ("improving", ctypes.c_uint32),
+        ("best_delta", ctypes.c_int64),
+        ("best_out_eid", ctypes.c_uint32),
+        ("best_in_eid", ctypes.c_uint32),
         ("ms_total", ctypes.c_double),
         ("reserved", ctypes.c_uint64),
     ]
@@ -447,6 +481,12 @@ def load():
             "ghs_forest_paths_query": (i32, [vp, u64, vp, vp, vp, vp, vp, vp, P(PathsQueryResult)]),
             "ghs_forest_paths_destroy": (i32, [vp]),
             "ghs_forest_paths_host": (i32, [u32, u64, vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, P(PathsQueryResult)]),
+            "ghs_forest_paths_info": (i32, [vp, P(PathsInfo)]),
+            # ABI 10 addition: replacement edges, bridges and the best swap of the rooted forest
+            "ghs_forest_replace_workspace_bytes": (sz, [u32, u64]),
+            "ghs_forest_replace_device": (i32, [vp, u64, vp, vp, vp, vp, vp, vp, sz, vp, P(ReplaceResult)]),
+            "ghs_forest_replace_host": (i32, [u32, u64, vp, vp, vp, vp, vp, vp, P(ReplaceResult)]),
+            "ghs_forest_replace_phases": (i32, [i32, P(ctypes.c_double)]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(L, name)

@@ -186,3 +186,59 @@ extern "C" int ghs_forest_paths_host(uint32_t n, uint64_t m, const uint32_t *u, 
   if (hops) GHS_HIP_CHECK(hipMemcpy(hops, x + off_h, q * 4, hipMemcpyDeviceToHost));
   return GHS_OK;
 }
+
+// Host-buffer form of the replacement edges (what a reference user asks when a link fails; the
+// reference reruns the protocol, ghs_implementation.py:442-490): copy in, root the flags, build the
+// jump-pointer index, replace, copy out. Public calls only.
+extern "C" int ghs_forest_replace_host(uint32_t n, uint64_t m, const uint32_t *u, const uint32_t *v, const uint32_t *w,
+                                       const uint8_t *in_mst, uint64_t *repl, uint32_t *repl_eid_by_edge,
+                                       ghs_replace_result_t *result) {
+  if (!result) GHS_FAIL(GHS_E_ARG, "result is NULL");
+  *result = ghs_replace_result_t{};
+  result->best_out_eid = result->best_in_eid = 0xffffffffu;
+  if (m >= (1ull << 31)) GHS_FAIL(GHS_E_ARG, "m must be < 2^31");
+  if (m && (!u || !v || !w || !in_mst)) GHS_FAIL(GHS_E_ARG, "NULL host pointer");
+  if (n == 0) return GHS_OK;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) GHS_FAIL(GHS_E_NODEVICE, "no HIP device");
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  hipStream_t st = nullptr;
+  // stage 1: the edges, the flags, the rooted arrays, the rooting's workspace
+  const size_t ws = m ? ghs_forest_root_workspace_bytes(n, m) : 0;
+  const size_t nb = al((size_t)n * 4);
+  const size_t off_u = 0, off_v = off_u + al(m * 4), off_w = off_v + al(m * 4), off_f = off_w + al(m * 4),
+               off_o = off_f + al(m ? m : 1), off_ws = off_o + 3 * nb, total = off_ws + al(ws ? ws : 1);
+  DevBuf buf;
+  GHS_HIP_CHECK(hipMalloc(&buf.p, total));
+  char *d = (char *)buf.p;
+  if (m) {
+    GHS_HIP_CHECK(hipMemcpyAsync(d + off_u, u, m * 4, hipMemcpyHostToDevice, st));
+    GHS_HIP_CHECK(hipMemcpyAsync(d + off_v, v, m * 4, hipMemcpyHostToDevice, st));
+    GHS_HIP_CHECK(hipMemcpyAsync(d + off_w, w, m * 4, hipMemcpyHostToDevice, st));
+    GHS_HIP_CHECK(hipMemcpyAsync(d + off_f, in_mst, m, hipMemcpyHostToDevice, st));
+  }
+  uint32_t *d_u = (uint32_t *)(d + off_u), *d_v = (uint32_t *)(d + off_v), *d_w = (uint32_t *)(d + off_w);
+  uint32_t *d_par = (uint32_t *)(d + off_o), *d_peid = (uint32_t *)(d + off_o + nb), *d_dep = (uint32_t *)(d + off_o + 2 * nb);
+  ghs_root_result_t rr;
+  int rc = ghs_forest_root_device(n, m, d_u, d_v, (uint8_t *)(d + off_f), d_par, d_peid, d_dep, nullptr, nullptr, d + off_ws,
+                                  ws, st, &rr);
+  if (rc) return rc;
+  if (!rr.is_forest) GHS_FAIL(GHS_E_ARG, "flags are not a forest");
+  // stage 2: the index, the cover levels, the answers
+  const size_t ib = ghs_forest_paths_index_bytes(n, rr.max_depth), rb = ghs_forest_replace_workspace_bytes(n, rr.max_depth);
+  const size_t off_rws = al(ib), off_r = off_rws + al(rb), off_e = off_r + al((size_t)n * 8);
+  DevBuf ibuf;
+  GHS_HIP_CHECK(hipMalloc(&ibuf.p, off_e + al(m ? m * 4 : 1)));
+  char *x = (char *)ibuf.p;
+  ghs_paths_result_t pr;
+  ghs_paths_t *h = nullptr;
+  rc = ghs_forest_paths_create(n, m, d_u, d_v, d_w, d_par, d_peid, d_dep, rr.max_depth, x, ib, st, &pr, &h);
+  if (rc) return rc;
+  rc = ghs_forest_replace_device(h, m, d_u, d_v, d_w, (uint64_t *)(x + off_r),
+                                 repl_eid_by_edge && m ? (uint32_t *)(x + off_e) : nullptr, x + off_rws, rb, st, result);
+  (void)ghs_forest_paths_destroy(h);
+  if (rc) return rc;
+  if (repl) GHS_HIP_CHECK(hipMemcpy(repl, x + off_r, (size_t)n * 8, hipMemcpyDeviceToHost));
+  if (repl_eid_by_edge && m) GHS_HIP_CHECK(hipMemcpy(repl_eid_by_edge, x + off_e, m * 4, hipMemcpyDeviceToHost));
+  return GHS_OK;
+}

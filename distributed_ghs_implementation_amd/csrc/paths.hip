@@ -462,6 +462,16 @@ int ghs_forest_paths_query(ghs_paths_t *h, uint64_t q, const uint32_t *d_a, cons
   return GHS_OK;
 }
 
+int ghs_forest_paths_info(const ghs_paths_t *h, ghs_paths_info_t *out) {
+  if (!h || h->magic != PA_MAGIC) GHS_FAIL(GHS_E_ARG, "handle is NULL or destroyed");
+  if (!out) GHS_FAIL(GHS_E_ARG, "out is NULL");
+  out->n = h->n;
+  out->levels = h->levels;
+  out->max_depth = h->max_depth;
+  out->d_index = h->index;
+  return GHS_OK;
+}
+
 int ghs_forest_paths_destroy(ghs_paths_t *h) {
   if (!h) return GHS_OK;
   if (h->magic != PA_MAGIC) GHS_FAIL(GHS_E_ARG, "handle is not a live ghs_paths_t");

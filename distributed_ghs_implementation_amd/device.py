@@ -422,6 +422,16 @@ class DeviceMST:
         edge / LCA / hop-count queries on the MSF."""
         return forest_paths(self.edges, self.in_mst)
 
+    def replacements(self, by_edge=True):
+        """`forest_replacements` of the engine's own flags (after `run()`): per forest edge the lightest
+        edge that takes its place when it fails, the bridges and the best swap. Returns (Replacements,
+        info); the index built on the way is released."""
+        index, _ = self.paths()
+        try:
+            return forest_replacements(self.edges, index, by_edge=by_edge)
+        finally:
+            index.close()
+
 
 def verify_msf(edges, in_mst):
     """Is `in_mst` THE minimum spanning forest of `edges`? Checked on the device, exactly, without a
@@ -727,6 +737,10 @@ class PathIndex:
                                                                 _ptr(ohops), _stream(), ctypes.byref(res)))
         return PathAnswers(okey, olca, ohops, res.as_dict())
 
+    def replacements(self, edges, by_edge=True):
+        """`forest_replacements(edges, self)`: the edge list must be the one this index was built over."""
+        return forest_replacements(edges, self, by_edge=by_edge)
+
     def close(self):
         if self._h:
             _native.load().ghs_forest_paths_destroy(self._h)
@@ -787,6 +801,68 @@ def forest_paths(edges, in_mst=None, rooted=None, max_depth=None):
                                                 _ptr(dep), max_depth, _ptr(index), ib, _stream(), ctypes.byref(res),
                                                 ctypes.byref(h)))
     return PathIndex(h, index, n, dev), res.as_dict()
+
+
+class Replacements:
+    """What `forest_replacements` returns, on the device. Every non-root vertex x stands for its parent
+    edge (x, parent[x]).
+    key: int64[n] holding the uint64 w << 32 | eid of the lightest non-forest edge that reconnects the
+    two halves when x's edge fails; all ones (-1) for a root and for a bridge. eid / w: its two halves as
+    int32 holding uint32 bit patterns. has_replacement: bool[n]. eid_by_edge: int32[m] (uint32 bits), for
+    a forest edge the replacement's eid, -1 for a bridge and for every non-forest edge; None when left
+    out. info: the fields of ghs_replace_result_t as a dict."""
+
+    def __init__(self, key, eid_by_edge, info=None):
+        self.key, self.eid_by_edge, self.info = key, eid_by_edge, info
+
+    @property
+    def eid(self):
+        return self.key.view(torch.int32).view(-1, 2)[:, 0]
+
+    @property
+    def w(self):
+        return self.key.view(torch.int32).view(-1, 2)[:, 1]
+
+    @property
+    def has_replacement(self):
+        return self.key != -1
+
+
+def forest_replacements(edges, index, by_edge=True):
+    """For every forest edge the edge that takes its place when it fails, on the device
+    (ghs_forest_replace_device, csrc/replace.hip). `index`: the PathIndex of `forest_paths` over this
+    edge list. A non-forest edge (a, b) inside one tree covers the forest edges of the path a .. b; per
+    forest edge the smallest covering key w << 32 | eid is its replacement, none makes it a bridge of
+    the graph. info counts tree_edges, covering_edges, cross_edges (non-forest edges between two
+    trees), bridges and improving (forest edges with a lighter replacement: 0 for the MSF), and names the
+    best swap: best_out_eid -> best_in_eid changes the total weight by best_delta, the least possible
+    (the second-best spanning forest); both eids are 0xffffffff when every forest edge is a bridge.
+    Returns (Replacements, info). A closed index or edges on another device raise ValueError. Runs on
+    torch's current stream; one query or replacement at a time per index."""
+    if not isinstance(index, PathIndex) or not index._h:
+        raise ValueError("the index is closed")
+    if edges.u is None:
+        raise ValueError("forest_replacements needs the COO form (u present); a CSR-only list is not supported")
+    if edges.device != index.device:
+        raise ValueError(f"the edges are on device {edges.device}, the index on device {index.device}")
+    if edges.n != index.n:
+        raise ValueError(f"the index covers {index.n} vertices, the edge list {edges.n}")
+    L = _native.load()
+    n, m, dev = edges.n, edges.m, index.device
+    pi = _native.PathsInfo()
+    _native.check(L.ghs_forest_paths_info(index._h, ctypes.byref(pi)))
+    _native.require_gpu()
+    with torch.cuda.device(dev):
+        wb = int(L.ghs_forest_replace_workspace_bytes(n, pi.max_depth))
+        key = torch.empty(n, dtype=torch.int64, device=dev)
+        eid = torch.empty(m, dtype=torch.int32, device=dev) if by_edge else None
+        ws = torch.empty(wb, dtype=torch.uint8, device=dev)
+        res = _native.ReplaceResult()
+        _native.check(L.ghs_forest_replace_device(index._h, m, _ptr(edges.u), _ptr(edges.v), _ptr(edges.w), _ptr(key),
+                                                  _ptr(eid) if by_edge else None, _ptr(ws), wb, _stream(),
+                                                  ctypes.byref(res)))
+    info = res.as_dict()
+    return Replacements(key, eid, info), info
 
 
 class DeviceBatch:

@@ -163,6 +163,61 @@ class MSTResult:
                "connected": lca != np.uint32(0xFFFFFFFF)}
         return (out, res.as_dict()) if return_info else out
 
+    def replacements(self, return_info=False, per_vertex=False):
+        """What takes each forest edge's place when it fails (ghs_forest_replace_host, on the GPU: the
+        flags rooted, a jump-pointer index, one cover pass over the edges). Returns a dict; the arrays
+        have one entry per canonical edge:
+          eid              uint32, for a forest edge the canonical id of the lightest edge (smallest
+                           (w, eid)) that reconnects the two halves; 0xffffffff for a bridge of the graph
+                           and for every non-forest edge
+          has_replacement  bool, eid != 0xffffffff
+          is_bridge        bool, a forest edge without a replacement
+          weight           the replacement's weight in the graph's own weights: for integer engine weights
+                           int64 with -1 where there is none; for a rank-mapped graph the dtype of
+                           graph.weights, NaN (floats) or 0 (integers) where there is none
+          second_best_weight  the weight of the second-best spanning forest: total_weight plus the
+                           smallest weight[replacement] - weight[edge] over the forest edges, in the
+                           graph's own weights; None when every forest edge is a bridge
+        per_vertex=True adds key: uint64 of n entries, the replacement's w << 32 | eid (engine weights)
+        of the edge from vertex x to its parent with every tree rooted at its smallest vertex (`rooted()`),
+        all ones for a root and for a bridge.
+        With the engine's forest no replacement is lighter than its edge (info["improving"] == 0).
+        return_info=True: (dict, the fields of ghs_replace_result_t as a dict; best_delta there is in
+        engine weights, ranks for a rank-mapped graph)."""
+        g = self.graph
+        L = _native.load()
+        if g.n:
+            _native.require_gpu()
+        flags = np.ascontiguousarray(self.in_mst, dtype=np.uint8)
+        eid = np.full(g.m, 0xFFFFFFFF, dtype=np.uint32)
+        key = np.full(g.n, (1 << 64) - 1, dtype=np.uint64) if per_vertex else None
+        res = _native.ReplaceResult()
+        _native.check(L.ghs_forest_replace_host(g.n, g.m, g.u.ctypes.data, g.v.ctypes.data, g.w.ctypes.data,
+                                                flags.ctypes.data, key.ctypes.data if per_vertex else None,
+                                                eid.ctypes.data, ctypes.byref(res)))
+        has = eid != np.uint32(0xFFFFFFFF)
+        at = np.where(has, eid, 0).astype(np.int64)
+        second = None
+        if g.weights is None:
+            weight = np.where(has, g.w[at].astype(np.int64), -1) if g.m else np.zeros(0, dtype=np.int64)
+            if has.any():
+                second = self.total_weight + int(res.best_delta)
+        elif g.m == 0:
+            weight = np.zeros(0, dtype=g.weights.dtype)
+        else:
+            none = np.nan if g.weights.dtype.kind == "f" else 0
+            weight = np.where(has, g.weights[at], g.weights.dtype.type(none))
+            if has.any():  # the least delta in the caller's units, not in ranks
+                if g.weights.dtype.kind == "f":
+                    second = self.total_weight + float((g.weights[at[has]] - g.weights[has]).min())
+                else:
+                    second = self.total_weight + min(int(x) - int(y) for x, y in zip(g.weights[at[has]], g.weights[has]))
+        out = {"eid": eid, "has_replacement": has, "is_bridge": self.in_mst & ~has, "weight": weight,
+               "second_best_weight": second}
+        if per_vertex:
+            out["key"] = key
+        return (out, res.as_dict()) if return_info else out
+
 
 def _weights_at_most(weights, t):
     """weights <= t as a mask; integer arrays are compared as integers, exactly at any magnitude."""

@@ -591,6 +591,85 @@ int ghs_forest_paths_destroy(ghs_paths_t *h);
 int ghs_forest_paths_host(uint32_t n, uint64_t m, const uint32_t *u, const uint32_t *v, const uint32_t *w,
                           const uint8_t *in_mst, uint64_t q, const uint32_t *a, const uint32_t *b,
                           uint64_t *key, uint32_t *lca, uint32_t *hops, ghs_paths_query_result_t *result);
+/* what a live handle indexes: n, K, the depth bound given to create and the device address of level 0
+ * (level k starts 16 k n bytes further; NULL when n == 0). Host only, no device work. NULL or
+ * destroyed handle, NULL out: GHS_E_ARG. */
+typedef struct ghs_paths_info {   /* 32 bytes */
+  uint64_t n;
+  uint64_t levels;          /* K (0 when n == 0) */
+  uint64_t max_depth;       /* the bound given to ghs_forest_paths_create */
+  const void *d_index;      /* the caller's index memory */
+} ghs_paths_info_t;
+int ghs_forest_paths_info(const ghs_paths_t *h, ghs_paths_info_t *out);
+
+/* ---- replacement edges: what takes e's place when e fails? (ABI 10 addition) ----------------------
+ * The path query looks from a non-forest edge into the forest; this is the opposite question, the
+ * other half of MST sensitivity analysis, and what a network asks when a link fails (the reference
+ * rebuilds from scratch, ghs_implementation.py:442-490). Input: the edge list and a rooted forest of
+ * it, as indexed by ghs_forest_paths_create. Every non-root vertex x stands for the forest edge
+ * (x, parent[x]). A non-forest edge f = (a, b) with both ends in one tree covers the forest edges on
+ * the tree path a .. b; an edge whose ends lie in different trees covers nothing and is only counted.
+ *   d_repl[x]                 the smallest key w[f] << 32 | f over the non-forest edges that cover x's
+ *                             edge: the edge that reconnects the two halves at the least weight.
+ *                             UINT64_MAX for a root, or when no edge covers it: a bridge of the graph.
+ *   d_repl_eid_by_edge[e]     (optional, m entries) for a forest edge e the low word of that key,
+ *                             0xffffffff for a bridge and for every non-forest edge.
+ * Edge e is a forest edge exactly when one of its ends is not a root and has e as the eid of its
+ * level-0 node. No flag array is read: the index was validated against u, v, w at create, which must
+ * be the same arrays (or copies) here.
+ * A forest edge whose replacement key is below its own key (`improving`) shows that the flags are not
+ * the MSF; with the engine's MSF improving == 0. The smallest w[repl] - w[e] over all forest edges is
+ * the best swap: total weight + best_delta is the weight of the second-best spanning forest.
+ * Algorithm (csrc/replace.hip): K levels of n uint64 slots cover[j][x] = "the 2^j forest edges going
+ * up from x are covered by this key", all UINT64_MAX at first; level 0 is d_repl itself. (1) One pass
+ * over the m edges finds each non-forest edge's meeting point with the query's lift-then-descend walk
+ * (four edges per lane), which gives L = depth[end] - depth[lca] per end; for L > 0 and j = floor(log2
+ * L) the key is min-ed into cover[j][end] and cover[j][end lifted by L - 2^j]: two ranges that overlap
+ * and are exactly the L edges. (2) For j = K - 1 .. 1 one launch over n mins a set cover[j][x] into
+ * cover[j-1][x] and cover[j-1][up_{j-1}(x)]. (3) One pass over n sets root slots, scatters the
+ * per-edge array, and reduces the counts and the best swap. Every minimum reads the slot first and
+ * skips the atomic when the slot is not larger (slots only decrease, so a stale read never hides a
+ * needed update). Integer minima commute: two calls give identical bytes. One host sync, at the end.
+ * Memory: ghs_forest_replace_workspace_bytes(n, max_depth) = 8 (K - 1) n rounded up to 256, + 256
+ * bytes of status, K = max(1, bit_length(max_depth)) (computed on the host, no GPU needed); max_depth
+ * is the bound the index was created with. The workspace is scratch. The index is only read, but the
+ * handle's one-call-at-a-time rule holds here too.
+ * Errors, in this order, before any device work (so they hold on a host without GPU): NULL or
+ * destroyed handle, NULL result, m >= 2^31, NULL or misaligned pointers (16 bytes for u / v / w / the
+ * workspace, 8 for d_repl, 4 for d_repl_eid_by_edge, which may be NULL): GHS_E_ARG; workspace short:
+ * GHS_E_NOMEM. An index over n == 0: no device work, d_repl may be NULL, GHS_OK when m == 0 (with
+ * m > 0 every endpoint is out of range). m == 0: d_u / d_v / d_w may be NULL, every slot is
+ * UINT64_MAX. An edge endpoint >= n: GHS_E_ARG ("edge endpoint out of range") after the sync; the
+ * outputs are then unspecified and nothing was read or written out of range. */
+typedef struct ghs_replace_result {   /* 64 bytes */
+  uint64_t tree_edges;      /* forest edges (non-root vertices) */
+  uint64_t covering_edges;  /* non-forest edges with both ends in one tree */
+  uint64_t cross_edges;     /* non-forest edges between two trees */
+  uint32_t bridges;         /* forest edges without a replacement */
+  uint32_t improving;       /* forest edges whose replacement key is below their own: 0 for the MSF */
+  int64_t  best_delta;      /* the smallest w[repl] - w[e]; 0 when every forest edge is a bridge */
+  uint32_t best_out_eid;    /* the forest edge of the best swap (ties: the smallest eid); 0xffffffff: none */
+  uint32_t best_in_eid;     /* its replacement; 0xffffffff: none */
+  double   ms_total;        /* host wall time of the call */
+  uint64_t reserved;        /* 0 */
+} ghs_replace_result_t;
+size_t ghs_forest_replace_workspace_bytes(uint32_t n, uint64_t max_depth);    /* host only, no GPU needed */
+int ghs_forest_replace_device(ghs_paths_t *h, uint64_t m, const uint32_t *d_u, const uint32_t *d_v, const uint32_t *d_w,
+                              uint64_t *d_repl /* n */, uint32_t *d_repl_eid_by_edge /* m or NULL */,
+                              void *d_workspace, size_t workspace_bytes, void *stream, ghs_replace_result_t *result);
+/* where the time of ghs_forest_replace_device goes, for benchmarks: enable != 0 makes this thread's later
+ * calls record HIP events around their four phases (five event records per call; off by default); ms,
+ * when not NULL, first receives the last recorded call's times in milliseconds: ms[0] the memsets,
+ * ms[1] the cover pass, ms[2] the K - 1 push-down launches, ms[3] the finish passes. Always GHS_OK. */
+int ghs_forest_replace_phases(int enable, double *ms /* 4, may be NULL */);
+/* the same for host arrays and flags: copy in, root the flags (ghs_forest_root_device without pre and
+ * size), build the index, replace, copy out; repl (n entries, indexed by vertex under the rooting at
+ * every tree's smallest vertex) and repl_eid_by_edge (m entries) may each be NULL. The argument errors
+ * above except the alignments (and NULL u / v / w / in_mst with m > 0), then GHS_E_NODEVICE without a
+ * GPU. n == 0: GHS_OK, no device work. Flags that close a cycle: GHS_E_ARG ("flags are not a forest"). */
+int ghs_forest_replace_host(uint32_t n, uint64_t m, const uint32_t *u, const uint32_t *v, const uint32_t *w,
+                            const uint8_t *in_mst, uint64_t *repl, uint32_t *repl_eid_by_edge,
+                            ghs_replace_result_t *result);
 
 /* device-side canonicity check: *ok = 1 iff u < v < n and (u, v) strictly ascending */
 int ghs_check_canonical(uint32_t n, uint64_t m, const uint32_t *d_u, const uint32_t *d_v, void *stream, int *ok);
