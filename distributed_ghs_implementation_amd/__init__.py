@@ -18,6 +18,12 @@ hop count): device.forest_paths, DeviceMST.paths, MSTResult.paths, CLI --paths /
 replacement edges (what takes a forest edge's place when it fails, the bridges, the best swap):
 device.forest_replacements, PathIndex.replacements, DeviceMST.replacements, MSTResult.replacements,
 CLI --replacements;
+tree distances (how far it is from a to b along the forest, the stretch of every graph edge over it,
+every tree's diameter, far ends, eccentricities and centre): device.forest_distances /
+forest_edge_distances / forest_diameters, PathIndex.wdepth / distances / edge_distances / diameters,
+DeviceMST.distances / edge_distances / diameters, MSTResult.distances / edge_distances / diameters,
+CLI --distances / --pairs, --diameters, --stretch (--hops counts edges: the only metric for rank-mapped
+weights);
 multi-GPU: distributed.DistributedMST. Float, negative and 64-bit
 weights: rank-mapped by graph.canonicalize on the host, or on the device with rank_weights=True
 (minimum_spanning_forest_edges, DeviceEdges.from_raw, canonicalize_device; device.weight_ranks).

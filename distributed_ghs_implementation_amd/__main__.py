@@ -37,6 +37,20 @@
                    the replacement's w << 32 | eid of the edge to its parent in the rooted forest), and
                    the counts tree_edges, covering_edges, cross_edges, bridges, improving, best_delta,
                    best_out_eid, best_in_eid
+    --distances OUT.npz --pairs PAIRS.npy
+                   after the solve, how far it is from a to b along the forest, on the GPU: OUT.npz
+                   holds a, b, dist (uint64: the sum of the weights on the path, 0 for a == b,
+                   2^64 - 1 for different components) and lca; --pairs as for --paths
+    --diameters OUT.npz
+                   after the solve, every tree's diameter on the GPU: root_of, diameter / end_a / end_b
+                   (indexed by root), ecc (every vertex's distance to the farthest vertex of its tree),
+                   roots, and num_trees, max_diameter, max_root, min_ecc, center
+    --stretch OUT.npz
+                   after the solve, the forest distance between the ends of every graph edge (dist,
+                   uint64 per canonical edge) and its summary: sum_dist (as a decimal string: it can
+                   pass 64 bits), sum_w, max_dist, max_eid, cross_edges, tight_edges
+    --hops         with --distances / --diameters: count edges instead of summing weights (required
+                   for rank-mapped weights, whose sums mean nothing)
 
     --batch-dir ROOT
                    many small graphs in one launch: every immediate subdirectory of ROOT holding
@@ -147,6 +161,13 @@ def main(argv=None):
                     help="with --paths: the vertex pairs to query, an integer array of shape (Q, 2)")
     ap.add_argument("--replacements", type=str, default=None, metavar="OUT.npz",
                     help="write every forest edge's replacement (eid_by_edge, key) and the bridge / best-swap counts")
+    ap.add_argument("--distances", type=str, default=None, metavar="OUT.npz",
+                    help="write the forest distances (a, b, dist, lca) of the --pairs after the solve")
+    ap.add_argument("--diameters", type=str, default=None, metavar="OUT.npz",
+                    help="write every tree's diameter, far ends and eccentricities after the solve")
+    ap.add_argument("--stretch", type=str, default=None, metavar="OUT.npz",
+                    help="write the forest distance of every graph edge (dist) and the stretch summary after the solve")
+    ap.add_argument("--hops", action="store_true", help="with --distances / --diameters: count edges, not weights")
     ap.add_argument("--gpus", type=int, default=1, help="GPUs driven by this one process (RCCL clique)")
     ap.add_argument("--generator", choices=["rmat", "grid"], default=None, help="synthetic graph instead of a file")
     ap.add_argument("--scale", type=int, default=16, help="R-MAT scale (2^scale vertices) / grid side k")
@@ -156,8 +177,11 @@ def main(argv=None):
         ap.error("--clusters and --max-weight exclude each other")
     if (args.clusters is not None or args.max_weight is not None) and not args.labels:
         ap.error("--clusters / --max-weight need --labels OUT.npy")
-    if (args.paths is None) != (args.pairs is None):
+    if (args.paths is not None and args.pairs is None) or (args.pairs is not None and args.paths is None
+                                                           and args.distances is None):
         ap.error("--paths OUT.npz and --pairs PAIRS.npy go together")
+    if args.distances is not None and args.pairs is None:
+        ap.error("--distances OUT.npz needs --pairs PAIRS.npy")
     if args.batch_dir is not None:
         return run_batch_dir(args)
 
@@ -283,6 +307,41 @@ def main(argv=None):
                     if pinfo["best_out_eid"] != 0xFFFFFFFF else "no swap")
             print(f"Replacements: {pinfo['tree_edges']} forest edges, {pinfo['bridges']} bridges, {swap}")
             print(f"Replacements saved to: {args.replacements}")
+    if args.distances:
+        import numpy as np
+
+        from .mst import MSTResult
+        pairs = np.load(args.pairs)
+        if pairs.ndim != 2 or pairs.shape[1] != 2 or pairs.dtype.kind not in "iu":
+            raise ValueError(f"{args.pairs}: an integer array of shape (Q, 2) expected, got {pairs.dtype} {pairs.shape}")
+        dist, lca, dinfo = MSTResult(g, np.asarray(flags), 0, rounds, [], ms).distances(
+            pairs[:, 0], pairs[:, 1], hops=args.hops, return_lca=True, return_info=True)
+        np.savez(args.distances, a=pairs[:, 0], b=pairs[:, 1], dist=dist, lca=lca)
+        if not args.quiet:
+            print(f"Distances: {len(pairs)} pairs, {dinfo['connected']} connected, max distance {dinfo['max_dist']}")
+            print(f"Distances saved to: {args.distances}")
+    if args.diameters:
+        import numpy as np
+
+        from .mst import MSTResult
+        tm, tinfo = MSTResult(g, np.asarray(flags), 0, rounds, [], ms).diameters(hops=args.hops, return_info=True)
+        np.savez(args.diameters, **tm, **{k: np.asarray(v) for k, v in tinfo.items() if k != "ms_total"})
+        if not args.quiet:
+            print(f"Diameters: {tinfo['num_trees']} trees, max diameter {tinfo['max_diameter']} (root {tinfo['max_root']}), "
+                  f"centre {tinfo['center']} at radius {tinfo['min_ecc']}")
+            print(f"Diameters saved to: {args.diameters}")
+    if args.stretch:
+        import numpy as np
+
+        from .mst import MSTResult
+        sd = MSTResult(g, np.asarray(flags), 0, rounds, [], ms).edge_distances()
+        summary = {k: np.asarray(-1 if v is None else v) for k, v in sd.items() if k not in ("dist", "stretch", "sum_dist")}
+        np.savez(args.stretch, dist=sd["dist"], sum_dist=np.asarray(str(sd["sum_dist"])), **summary)
+        if not args.quiet:
+            avg = sd["sum_dist"] / sd["sum_w"] if sd["sum_w"] else float("nan")
+            print(f"Stretch: {g.m} edges, sum dist {sd['sum_dist']}, sum w {sd['sum_w']} (average {avg:.6g}), "
+                  f"max dist {sd['max_dist']} at edge {sd['max_eid']}, {sd['tight_edges']} tight")
+            print(f"Stretch saved to: {args.stretch}")
     status = 0
     if args.check:
         from .verify import format_report, verify_forest

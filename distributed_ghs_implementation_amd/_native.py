@@ -33,6 +33,9 @@ GHS_W_UINT64 = 3
 GHS_CUT_NONE = 0
 GHS_CUT_WEIGHT = 1
 GHS_CUT_COUNT = 2
+# the metrics of ghs_forest_wdepth_device (include/ghs_mst.h GHS_DIST_*)
+GHS_DIST_WEIGHT = 0
+GHS_DIST_HOPS = 1
 
 _ERR_NAMES = {
     GHS_E_ARG: "GHS_E_ARG", GHS_E_NONCANON: "GHS_E_NONCANON", GHS_E_HIP: "GHS_E_HIP",
@@ -67,6 +70,8 @@ EXPORTED_SYMBOLS = (
     "ghs_forest_paths_host", "ghs_forest_paths_info",
     "ghs_forest_replace_workspace_bytes", "ghs_forest_replace_device", "ghs_forest_replace_host",
     "ghs_forest_replace_phases",
+    "ghs_forest_dist_workspace_bytes", "ghs_forest_wdepth_device", "ghs_forest_dist_query",
+    "ghs_forest_edge_dist_device", "ghs_forest_diameter_device", "ghs_forest_dist_host", "ghs_forest_diameter_host",
 )
 
 
@@ -269,6 +274,60 @@ class ReplaceResult(ctypes.Structure):
         ("best_delta", ctypes.c_int64),
         ("best_out_eid", ctypes.c_uint32),
         ("best_in_eid", ctypes.c_uint32),
+        ("ms_total", ctypes.c_double),
+        ("reserved", ctypes.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class DistQueryResult(ctypes.Structure):
+    """ghs_dist_query_result_t: one ghs_forest_dist_query / ghs_forest_dist_host call."""
+    _fields_ = [
+        ("queries", ctypes.c_uint64),
+        ("connected", ctypes.c_uint64),
+        ("disconnected", ctypes.c_uint64),
+        ("max_dist", ctypes.c_uint64),
+        ("ms_total", ctypes.c_double),
+        ("reserved", ctypes.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class EdgeDistResult(ctypes.Structure):
+    """ghs_edge_dist_result_t: one ghs_forest_edge_dist_device call. as_dict joins the two words of the
+    128-bit sum into the Python int sum_dist."""
+    _fields_ = [
+        ("edges", ctypes.c_uint64),
+        ("sum_dist_lo", ctypes.c_uint64),
+        ("sum_dist_hi", ctypes.c_uint64),
+        ("sum_w", ctypes.c_uint64),
+        ("max_dist", ctypes.c_uint64),
+        ("cross_edges", ctypes.c_uint64),
+        ("tight_edges", ctypes.c_uint64),
+        ("max_eid", ctypes.c_uint32),
+        ("reserved32", ctypes.c_uint32),
+        ("ms_total", ctypes.c_double),
+        ("reserved", ctypes.c_uint64),
+    ]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
+        d["sum_dist"] = (d.pop("sum_dist_hi") << 64) | d.pop("sum_dist_lo")
+        return d
+
+
+class DiameterResult(ctypes.Structure):
+    """ghs_diameter_result_t: one ghs_forest_diameter_device / ghs_forest_diameter_host call."""
+    _fields_ = [
+        ("num_trees", ctypes.c_uint64),
+        ("max_diameter", ctypes.c_uint64),
+        ("min_ecc", ctypes.c_uint64),
+        ("max_root", ctypes.c_uint32),
+        ("center", ctypes.c_uint32),
         ("ms_total", ctypes.c_double),
         ("reserved", ctypes.c_uint64),
     ]
@@ -487,6 +546,14 @@ def load():
             "ghs_forest_replace_device": (i32, [vp, u64, vp, vp, vp, vp, vp, vp, sz, vp, P(ReplaceResult)]),
             "ghs_forest_replace_host": (i32, [u32, u64, vp, vp, vp, vp, vp, vp, P(ReplaceResult)]),
             "ghs_forest_replace_phases": (i32, [i32, P(ctypes.c_double)]),
+            # ABI 10 addition: tree distances, edge stretch and tree diameters on the rooted forest
+            "ghs_forest_dist_workspace_bytes": (sz, [u32, u64]),
+            "ghs_forest_wdepth_device": (i32, [vp, u32, vp, vp, sz, vp]),
+            "ghs_forest_dist_query": (i32, [vp, vp, u64, vp, vp, vp, vp, P(DistQueryResult), vp]),
+            "ghs_forest_edge_dist_device": (i32, [vp, vp, u64, vp, vp, vp, vp, P(EdgeDistResult), vp]),
+            "ghs_forest_diameter_device": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, sz, P(DiameterResult), vp]),
+            "ghs_forest_dist_host": (i32, [u32, u64, vp, vp, vp, vp, u32, u64, vp, vp, vp, vp, P(DistQueryResult)]),
+            "ghs_forest_diameter_host": (i32, [u32, u64, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, P(DiameterResult)]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(L, name)

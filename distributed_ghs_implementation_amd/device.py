@@ -432,6 +432,34 @@ class DeviceMST:
         finally:
             index.close()
 
+    def distances(self, a, b, hops=False):
+        """`forest_distances` on the engine's own flags (after `run()`): how far it is from a[i] to
+        b[i] along the MSF, as a uint64 tensor. The index built on the way is released; keep a
+        `paths()` index and call `PathIndex.distances` for repeated queries."""
+        index, _ = self.paths()
+        try:
+            return forest_distances(index, a, b, hops=hops)
+        finally:
+            index.close()
+
+    def edge_distances(self, by_edge=True):
+        """`forest_edge_distances` of the graph's own edges over the engine's own flags (after `run()`):
+        an EdgeDistances with the per-edge distances, their stretch and the exact sums."""
+        index, _ = self.paths()
+        try:
+            return forest_edge_distances(self.edges, index, by_edge=by_edge)
+        finally:
+            index.close()
+
+    def diameters(self, ecc=True, hops=False):
+        """`forest_diameters` of the engine's own flags (after `run()`): a TreeMetrics with every
+        tree's diameter, far ends and eccentricities, and the centre of the widest tree."""
+        index, _ = self.paths()
+        try:
+            return forest_diameters(index, ecc=ecc, hops=hops)
+        finally:
+            index.close()
+
 
 def verify_msf(edges, in_mst):
     """Is `in_mst` THE minimum spanning forest of `edges`? Checked on the device, exactly, without a
@@ -708,8 +736,12 @@ class PathIndex:
     index tensor alive; `close()` (or deletion) destroys the native handle. One query at a time per
     index: the calls' status block lives in the index."""
 
-    def __init__(self, handle, index, n, device):
+    def __init__(self, handle, index, n, device, ranked=False):
         self._h, self._index, self.n, self.device = handle, index, int(n), device
+        # the index was built over rank-mapped weights (edges.weights set): its keys hold ranks
+        self.ranked = bool(ranked)
+        self._wdepth = {}
+        self.last_distance_info = None
 
     def query(self, a, b, key=True, lca=True, hops=True):
         """a, b: int32 (uint32 bit patterns) or int64 GPU tensors of equal length, or ints. Returns a
@@ -741,11 +773,52 @@ class PathIndex:
         """`forest_replacements(edges, self)`: the edge list must be the one this index was built over."""
         return forest_replacements(edges, self, by_edge=by_edge)
 
+    def _metric(self, hops):
+        if not hops and self.ranked:
+            raise ValueError("the index was built over rank-mapped weights (edges.weights is set): a sum of ranks "
+                             "means nothing; use hops=True for distances in edges")
+        return _native.GHS_DIST_HOPS if hops else _native.GHS_DIST_WEIGHT
+
+    def wdepth(self, hops=False):
+        """Every vertex's distance to its tree's root (ghs_forest_wdepth_device, csrc/dist.hip): a uint64
+        GPU tensor of n entries, the sum of the weights on the path (hops=True: the number of edges),
+        0 for a root. Built on the first call by pointer doubling over the index's levels and cached on
+        the index, one array per metric. Rank-mapped weights raise ValueError unless hops=True."""
+        if not self._h:
+            raise ValueError("the index is closed")
+        metric = self._metric(hops)
+        if metric not in self._wdepth:
+            L = _native.load()
+            pi = _native.PathsInfo()
+            _native.check(L.ghs_forest_paths_info(self._h, ctypes.byref(pi)))
+            _native.require_gpu()
+            with torch.cuda.device(self.device):
+                wb = int(L.ghs_forest_dist_workspace_bytes(self.n, pi.max_depth))
+                wd = torch.empty(self.n, dtype=torch.int64, device=self.device)
+                ws = torch.empty(wb, dtype=torch.uint8, device=self.device)
+                _native.check(L.ghs_forest_wdepth_device(self._h, metric, _ptr(wd), _ptr(ws), wb, _stream()))
+            del ws
+            self._wdepth[metric] = wd.view(torch.uint64)
+        return self._wdepth[metric]
+
+    def distances(self, a, b, hops=False, lca=False):
+        """`forest_distances(self, a, b)`: the distance between a[i] and b[i] along the forest."""
+        return forest_distances(self, a, b, hops=hops, lca=lca)
+
+    def edge_distances(self, edges, by_edge=True):
+        """`forest_edge_distances(edges, self)`: the edge list must be the one this index was built over."""
+        return forest_edge_distances(edges, self, by_edge=by_edge)
+
+    def diameters(self, ecc=True, hops=False):
+        """`forest_diameters(self)`: diameter, far ends and eccentricities of every tree."""
+        return forest_diameters(self, ecc=ecc, hops=hops)
+
     def close(self):
         if self._h:
             _native.load().ghs_forest_paths_destroy(self._h)
             self._h = None
         self._index = None
+        self._wdepth = {}
 
     def __del__(self):
         try:
@@ -800,7 +873,7 @@ def forest_paths(edges, in_mst=None, rooted=None, max_depth=None):
         _native.check(L.ghs_forest_paths_create(n, m, _ptr(edges.u), _ptr(edges.v), _ptr(edges.w), _ptr(par), _ptr(peid),
                                                 _ptr(dep), max_depth, _ptr(index), ib, _stream(), ctypes.byref(res),
                                                 ctypes.byref(h)))
-    return PathIndex(h, index, n, dev), res.as_dict()
+    return PathIndex(h, index, n, dev, ranked=edges.weights is not None), res.as_dict()
 
 
 class Replacements:
@@ -863,6 +936,159 @@ def forest_replacements(edges, index, by_edge=True):
                                                   ctypes.byref(res)))
     info = res.as_dict()
     return Replacements(key, eid, info), info
+
+
+def _live_index(index):
+    if not isinstance(index, PathIndex) or not index._h:
+        raise ValueError("the index is closed")
+    return index
+
+
+def forest_distances(index, a, b, hops=False, lca=False):
+    """How far is it from a[i] to b[i] along the forest? On the device (ghs_forest_dist_query,
+    csrc/dist.hip): dist = wd[a] + wd[b] - 2 wd[lca(a, b)] over `index.wdepth(hops)`, one fused kernel
+    (the path query's LCA walk, then three gathers). `index`: the PathIndex of `forest_paths`.
+    a, b: int32 (uint32 bit patterns) or int64 GPU tensors of equal length, or ints.
+    Returns a uint64 GPU tensor, one entry per pair: 0 where a == b, all ones (UINT64_MAX) where the
+    ends are in different trees. Every finite distance is below 2^63, so `.view(torch.int64)` is exact,
+    with -1 for different trees. hops=True counts edges instead of summing weights; rank-mapped weights
+    (`edges.weights` set) raise ValueError unless hops=True. lca=True: returns (dist, lca) with lca
+    int32 (uint32 bits, -1 for different trees). An id >= n raises GHSError (GHS_E_ARG). Runs on torch's
+    current stream; one call at a time per index. `index.last_distance_info` keeps the fields of
+    ghs_dist_query_result_t (queries, connected, disconnected, max_dist, ms_total)."""
+    index = _live_index(index)
+    wd = index.wdepth(hops)
+    dev = index.device
+    ta = torch.as_tensor(a, device=dev).reshape(-1) if not isinstance(a, torch.Tensor) else a
+    tb = torch.as_tensor(b, device=dev).reshape(-1) if not isinstance(b, torch.Tensor) else b
+    for name, t in (("a", ta), ("b", tb)):
+        if t.dim() != 1 or t.device != dev:
+            raise ValueError(f"{name}: a one-dimensional tensor on the index's device (or an int) expected")
+    if ta.numel() != tb.numel():
+        raise ValueError("a and b must have equal length")
+    ta, tb = _as_u32_tensor(ta, "a"), _as_u32_tensor(tb, "b")
+    q = int(ta.numel())
+    if q >= (1 << 32):
+        raise ValueError("at most 2^32 - 1 pairs")
+    with torch.cuda.device(dev):
+        odist = torch.empty(q, dtype=torch.int64, device=dev)
+        olca = torch.empty(q, dtype=torch.int32, device=dev) if lca else None
+        res = _native.DistQueryResult()
+        _native.check(_native.load().ghs_forest_dist_query(index._h, _ptr(wd), q, _ptr(ta), _ptr(tb), _ptr(odist),
+                                                           _ptr(olca), ctypes.byref(res), _stream()))
+    index.last_distance_info = res.as_dict()
+    odist = odist.view(torch.uint64)
+    return (odist, olca) if lca else odist
+
+
+class EdgeDistances:
+    """What `forest_edge_distances` returns. dist: uint64[m] on the device, the forest distance between
+    every graph edge's ends (all ones for an edge between two trees); None when left out. w: the edge
+    weights (int32 holding uint32 bits). info: the fields of ghs_edge_dist_result_t as a dict, with the
+    128-bit sum as the Python int sum_dist: edges, sum_dist, sum_w, max_dist, max_eid, cross_edges,
+    tight_edges, ms_total."""
+
+    def __init__(self, dist, w, info=None):
+        self.dist, self.w, self.info = dist, w, info
+
+    def stretch(self):
+        """dist / w per edge as float64 on the device: inf where w == 0 and dist > 0 (and for an edge
+        between two trees), 1.0 where both are 0. A forest edge has stretch 1."""
+        if self.dist is None:
+            raise ValueError("the call was made without the per-edge array (by_edge=False)")
+        d = self.dist.view(torch.int64)
+        w = self.w.to(torch.int64) & 0xFFFFFFFF
+        s = d.to(torch.float64) / w.to(torch.float64)
+        s = torch.where((d == 0) & (w == 0), torch.ones_like(s), s)
+        return torch.where(d < 0, torch.full_like(s, float("inf")), s)
+
+    def average_stretch(self):
+        """sum_dist / sum_w over the edges inside one tree (the weighted average stretch), as a float;
+        nan when the weights sum to 0."""
+        return self.info["sum_dist"] / self.info["sum_w"] if self.info["sum_w"] else float("nan")
+
+
+def forest_edge_distances(edges, index, by_edge=True):
+    """The forest distance between the ends of every edge of the graph, on the device
+    (ghs_forest_edge_dist_device, csrc/dist.hip): what the stretch dist / w of a spanning forest is
+    made of. `index`: the PathIndex of `forest_paths` over this edge list. The kernel stays in exact
+    integers: info carries sum_dist (a Python int, 128 bits wide on the device), sum_w, max_dist with
+    the smallest edge id attaining it (max_eid), cross_edges (ends in different trees: 0 for a spanning
+    forest) and tight_edges (dist == w: every forest edge and its ties). by_edge=False leaves the
+    per-edge array out (the arg-max then repeats the walk). Rank-mapped weights (`edges.weights` set)
+    raise ValueError: a sum of ranks means nothing.
+    Returns an EdgeDistances (.dist, .stretch(), .info). Runs on torch's current stream; one call at a
+    time per index."""
+    index = _live_index(index)
+    if edges.u is None:
+        raise ValueError("forest_edge_distances needs the COO form (u present); a CSR-only list is not supported")
+    if edges.device != index.device:
+        raise ValueError(f"the edges are on device {edges.device}, the index on device {index.device}")
+    if edges.n != index.n:
+        raise ValueError(f"the index covers {index.n} vertices, the edge list {edges.n}")
+    if edges.weights is not None or index.ranked:
+        raise ValueError("rank-mapped weights (edges.weights is set): a sum of ranks means nothing; "
+                         "use distances(..., hops=True) for distances in edges")
+    wd = index.wdepth(False)
+    m, dev = edges.m, index.device
+    with torch.cuda.device(dev):
+        dist = torch.empty(m, dtype=torch.int64, device=dev) if by_edge else None
+        res = _native.EdgeDistResult()
+        _native.check(_native.load().ghs_forest_edge_dist_device(index._h, _ptr(wd), m, _ptr(edges.u), _ptr(edges.v),
+                                                                 _ptr(edges.w), _ptr(dist), ctypes.byref(res), _stream()))
+    return EdgeDistances(dist.view(torch.uint64) if by_edge else None, edges.w, res.as_dict())
+
+
+class TreeMetrics:
+    """What `forest_diameters` returns, on the device. root_of: int32[n] (uint32 bits), every vertex's
+    root. diameter: uint64[n] indexed by root (0 in every other slot). end_a / end_b: int32[n] indexed
+    by root, the two far ends p and q (-1 in every other slot). ecc: uint64[n], every vertex's distance
+    to the farthest vertex of its tree; None when left out. info: the fields of ghs_diameter_result_t
+    as a dict: num_trees, max_diameter, max_root, min_ecc, center, ms_total."""
+
+    def __init__(self, root_of, diameter, end_a, end_b, ecc, info=None):
+        self.root_of, self.diameter, self.end_a, self.end_b, self.ecc, self.info = root_of, diameter, end_a, end_b, ecc, info
+
+    def roots(self):
+        """The roots in ascending order (int64 GPU tensor): the slots of diameter / end_a / end_b in use."""
+        return torch.nonzero(self.end_a != -1).reshape(-1)
+
+    def center(self):
+        """(vertex, radius) of the tree with the largest diameter: the vertex with the smallest
+        eccentricity (ties: the smallest id) and that eccentricity. None for an empty graph."""
+        if not self.info or not self.info["num_trees"]:
+            return None
+        return self.info["center"], self.info["min_ecc"]
+
+
+def forest_diameters(index, ecc=True, hops=False):
+    """Diameter, far ends and eccentricities of every tree of the forest, on the device
+    (ghs_forest_diameter_device, csrc/dist.hip). Two sweeps, exact for non-negative weights: p = the
+    vertex farthest from the root, q = the vertex farthest from p (ties: the smallest id), diameter =
+    dist(p, q), ecc[v] = max(dist(v, p), dist(v, q)). A single-vertex tree has diameter 0 and both ends
+    equal to itself. `index`: the PathIndex of `forest_paths`. ecc=False leaves the eccentricities out
+    of the result (the centre is found either way). hops=True counts edges; rank-mapped weights
+    (`edges.weights` set) raise ValueError unless hops=True.
+    Returns a TreeMetrics (.root_of, .diameter, .end_a, .end_b, .ecc, .center(), .info). Runs on torch's
+    current stream; one call at a time per index."""
+    index = _live_index(index)
+    wd = index.wdepth(hops)
+    L = _native.load()
+    n, dev = index.n, index.device
+    pi = _native.PathsInfo()
+    _native.check(L.ghs_forest_paths_info(index._h, ctypes.byref(pi)))
+    with torch.cuda.device(dev):
+        wb = int(L.ghs_forest_dist_workspace_bytes(n, pi.max_depth))
+        root_of, end_a, end_b = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
+        diam = torch.empty(n, dtype=torch.int64, device=dev)
+        oecc = torch.empty(n, dtype=torch.int64, device=dev) if ecc else None
+        ws = torch.empty(wb, dtype=torch.uint8, device=dev)
+        res = _native.DiameterResult()
+        _native.check(L.ghs_forest_diameter_device(index._h, _ptr(wd), _ptr(root_of), _ptr(diam), _ptr(end_a), _ptr(end_b),
+                                                   _ptr(oecc), _ptr(ws), wb, ctypes.byref(res), _stream()))
+    del ws
+    return TreeMetrics(root_of, diam.view(torch.uint64), end_a, end_b, oecc.view(torch.uint64) if ecc else None,
+                       res.as_dict())
 
 
 class DeviceBatch:

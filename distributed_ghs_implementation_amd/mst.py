@@ -218,6 +218,93 @@ class MSTResult:
             out["key"] = key
         return (out, res.as_dict()) if return_info else out
 
+    def _dist_metric(self, hops):
+        if not hops and self.graph.weights is not None:
+            raise ValueError("the graph's weights are rank-mapped (graph.weights is set): a sum of ranks means "
+                             "nothing; use hops=True for distances in edges")
+        return _native.GHS_DIST_HOPS if hops else _native.GHS_DIST_WEIGHT
+
+    def distances(self, a, b, hops=False, return_lca=False, return_info=False):
+        """How far it is from a[i] to b[i] along the forest (ghs_forest_dist_host, on the GPU: the flags
+        rooted, a jump-pointer index, the weighted depth by pointer doubling, one fused query). a, b:
+        integer arrays of equal length (or ints) with ids in [0, n). Returns a numpy uint64 array, one
+        entry per pair: the sum of the weights on the path (hops=True: the number of edges), 0 where
+        a == b, 2^64 - 1 where a and b are in different trees. A rank-mapped graph (graph.weights set)
+        raises ValueError unless hops=True. return_lca=True: (dist, lca) with lca the lowest common
+        ancestor under the rooting at every tree's smallest vertex (0xffffffff for different trees).
+        return_info=True appends the fields of ghs_dist_query_result_t as a dict."""
+        g = self.graph
+        metric = self._dist_metric(hops)
+        qa, qb = np.atleast_1d(np.asarray(a)), np.atleast_1d(np.asarray(b))
+        if qa.ndim != 1 or qa.shape != qb.shape or qa.dtype.kind not in "iu" or qb.dtype.kind not in "iu":
+            raise ValueError("a, b: one-dimensional integer arrays of equal length (or ints) expected")
+        q = len(qa)
+        if q and (int(qa.min()) < 0 or int(qb.min()) < 0 or int(qa.max()) >= g.n or int(qb.max()) >= g.n):
+            raise ValueError(f"a, b: vertex ids must be in [0, {g.n})")
+        qa, qb = np.ascontiguousarray(qa, dtype=np.uint32), np.ascontiguousarray(qb, dtype=np.uint32)
+        L = _native.load()
+        if q:
+            _native.require_gpu()
+        flags = np.ascontiguousarray(self.in_mst, dtype=np.uint8)
+        dist = np.empty(q, dtype=np.uint64)
+        lca = np.empty(q, dtype=np.uint32)
+        res = _native.DistQueryResult()
+        _native.check(L.ghs_forest_dist_host(g.n, g.m, g.u.ctypes.data, g.v.ctypes.data, g.w.ctypes.data,
+                                             flags.ctypes.data, metric, q, qa.ctypes.data, qb.ctypes.data,
+                                             dist.ctypes.data, lca.ctypes.data, ctypes.byref(res)))
+        out = (dist, lca) if return_lca else (dist,)
+        if return_info:
+            out += (res.as_dict(),)
+        return out if len(out) > 1 else out[0]
+
+    def edge_distances(self):
+        """The forest distance between the ends of every edge of the graph, and what the forest's
+        stretch is made of (ghs_forest_dist_host with the graph's own edges as the pairs). Returns a
+        dict: dist (uint64 per canonical edge, 2^64 - 1 for an edge between two trees), stretch (float64:
+        dist / w, inf where w == 0 and dist > 0 and for an edge between two trees, 1.0 where both are 0),
+        and over the edges inside one tree the exact Python ints sum_dist and sum_w, max_dist with the
+        smallest edge id attaining it (max_eid, None when there is no such edge), cross_edges and
+        tight_edges (dist == w: every forest edge and its ties). A rank-mapped graph raises ValueError."""
+        g = self.graph
+        self._dist_metric(False)
+        dist = self.distances(g.u, g.v) if g.m else np.zeros(0, dtype=np.uint64)
+        inside = dist != np.uint64((1 << 64) - 1)
+        w = g.w.astype(np.uint64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            stretch = dist.astype(np.float64) / w.astype(np.float64)
+        stretch[(dist == 0) & (w == 0)] = 1.0
+        stretch[~inside] = np.inf
+        far = int(dist[inside].max()) if inside.any() else 0
+        return {"dist": dist, "stretch": stretch,
+                "sum_dist": sum(int(x) for x in dist[inside]), "sum_w": int(w[inside].sum(dtype=np.uint64)),
+                "max_dist": far, "max_eid": int(np.flatnonzero(inside & (dist == far))[0]) if inside.any() else None,
+                "cross_edges": int((~inside).sum()), "tight_edges": int((inside & (dist == w)).sum())}
+
+    def diameters(self, hops=False, return_info=False):
+        """Diameter, far ends and eccentricities of every tree of the forest (ghs_forest_diameter_host,
+        on the GPU; two sweeps, exact for non-negative weights, ties to the smallest id). Returns a dict
+        of numpy arrays of n entries under the rooting at every tree's smallest vertex: root_of (uint32),
+        diameter (uint64, indexed by root, 0 elsewhere), end_a / end_b (uint32, indexed by root, the two
+        far ends, 0xffffffff elsewhere), ecc (uint64, every vertex's distance to the farthest vertex of
+        its tree), and roots (the root ids in ascending order). hops=True counts edges; a rank-mapped
+        graph raises ValueError unless hops=True. return_info=True: (dict, the fields of
+        ghs_diameter_result_t as a dict: num_trees, max_diameter, max_root, min_ecc, center, ms_total)."""
+        g = self.graph
+        metric = self._dist_metric(hops)
+        L = _native.load()
+        if g.n:
+            _native.require_gpu()
+        flags = np.ascontiguousarray(self.in_mst, dtype=np.uint8)
+        out = {"root_of": np.empty(g.n, dtype=np.uint32), "diameter": np.empty(g.n, dtype=np.uint64),
+               "end_a": np.empty(g.n, dtype=np.uint32), "end_b": np.empty(g.n, dtype=np.uint32),
+               "ecc": np.empty(g.n, dtype=np.uint64)}
+        res = _native.DiameterResult()
+        _native.check(L.ghs_forest_diameter_host(g.n, g.m, g.u.ctypes.data, g.v.ctypes.data, g.w.ctypes.data,
+                                                 flags.ctypes.data, metric, *[out[k].ctypes.data for k in out],
+                                                 ctypes.byref(res)))
+        out["roots"] = np.flatnonzero(out["root_of"] == np.arange(g.n, dtype=np.uint32)).astype(np.uint32)
+        return (out, res.as_dict()) if return_info else out
+
 
 def _weights_at_most(weights, t):
     """weights <= t as a mask; integer arrays are compared as integers, exactly at any magnitude."""

@@ -671,6 +671,133 @@ int ghs_forest_replace_host(uint32_t n, uint64_t m, const uint32_t *u, const uin
                             const uint8_t *in_mst, uint64_t *repl, uint32_t *repl_eid_by_edge,
                             ghs_replace_result_t *result);
 
+/* ---- tree distances: how far is it from a to b? (ABI 10 addition) ----------------------------------
+ * The path query gives the heaviest edge between a and b; these calls give the sum of the edges, the
+ * number a spanning-tree user asks for first (a reference node knows its level and its in_branch only,
+ * ghs_implementation.py:63,212, and would walk edge by edge). Built on it: the stretch dist_T(u, v) / w
+ * of every graph edge over the forest, and the diameter, the two far ends, every vertex's eccentricity
+ * and the centre of every tree. All calls work on the index of ghs_forest_paths_create (csrc/dist.hip
+ * reaches it through ghs_forest_paths_info), read it only, and obey the handle's one-call-at-a-time
+ * rule: the two calls without a workspace keep their counters in the index's status block. Exact
+ * integers throughout; two calls give identical bytes.
+ *
+ * Weighted depth (ghs_forest_wdepth_device): d_wdepth[v] = the sum of the weights on the path from v
+ * to its tree's root, 0 for a root. metric = GHS_DIST_WEIGHT uses the weights in the index's level-0
+ * keys (key >> 32); GHS_DIST_HOPS uses 1 per edge, so the result is the depth. Nothing is
+ * level-synchronous over the depth: with S_k[v] = the sum of the (up to) 2^k edges going up from v,
+ * S_{k+1}[v] = S_k[v] + S_k[up_k[v]]; a root points at itself with key 0 and up_k of a vertex with
+ * fewer than 2^k ancestors is its root, so a jump past a root adds 0. K launches over n, ping-ponging
+ * between d_wdepth and one workspace slab; 2^K > max_depth makes the last one final. The sums are exact
+ * in uint64: depth < 2^31 and w < 2^32 keep every sum below 2^63, so wd[a] + wd[b] never wraps either.
+ * One host sync. The array is the caller's: the later calls take it as an argument, read its values
+ * and never use them as indices (a wrong array gives wrong distances, nothing else).
+ * Workspace: ghs_forest_dist_workspace_bytes(n, max_depth) = 8 n rounded up to 256, + 256 bytes of
+ * status, at any K (computed on the host, no GPU needed; max_depth is the bound the index was created
+ * with). One formula for this call and for ghs_forest_diameter_device. The workspace is scratch.
+ * Errors, in this order, before any device work (so they hold on a host without GPU): NULL or
+ * destroyed handle, unknown metric, NULL or misaligned pointers (8 bytes for d_wdepth, 16 for the
+ * workspace): GHS_E_ARG; workspace short: GHS_E_NOMEM. An index over n == 0: GHS_OK, no device work,
+ * d_wdepth may be NULL.
+ *
+ * Distance queries (ghs_forest_dist_query): q pairs d_a[i], d_b[i] -> d_dist[i] = wd[a] + wd[b] -
+ * 2 wd[lca(a, b)]: 0 when a == b, UINT64_MAX when a and b are in different trees. d_lca (may be NULL)
+ * receives the lowest common ancestor as the path query defines it (a when a == b, 0xffffffff across
+ * trees). One fused kernel: the path query's LCA walk without its keys (four pairs per lane advancing
+ * together on 16-byte node loads), then the three 8-byte gathers; no LCA array goes through memory.
+ * One host sync. An id >= n anywhere in d_a / d_b: GHS_E_ARG ("vertex id out of range") after the sync;
+ * the outputs are then unspecified and nothing was read or written out of range.
+ * Errors before any device work: NULL result, NULL or destroyed handle, q >= 2^32, then (q > 0) NULL
+ * d_a / d_b / d_dist / d_wdepth, misaligned pointers (4 bytes for a / b / lca, 8 for wdepth / dist):
+ * GHS_E_ARG. q == 0: GHS_OK, no device work, every pointer may be NULL. An index over n == 0 with
+ * q > 0: GHS_E_ARG (every id is out of range).
+ *
+ * The graph's own edges (ghs_forest_edge_dist_device): the canonical list as m pairs (u[e], v[e]) with
+ * their weights; d_dist_by_edge[e] (may be NULL) = dist(u[e], v[e]), UINT64_MAX for an edge between two
+ * trees. The sums and the maximum run over the edges with both ends in one tree. The stretch of edge e
+ * is dist / w; ratios are left to the caller, the kernel stays in integers. tight_edges counts dist ==
+ * w: every forest edge, and with positive weights only forest edges and their ties. The same walk as
+ * the query; the smallest eid attaining max_dist is found by a second pass (over d_dist_by_edge when it
+ * was written; otherwise the walk is repeated, which doubles the call's time). One host sync.
+ * Errors before any device work: NULL result, NULL or destroyed handle, m >= 2^31, then (m > 0) NULL
+ * d_u / d_v / d_w / d_wdepth, misaligned pointers (16 bytes for u / v / w, 8 for wdepth /
+ * dist_by_edge): GHS_E_ARG. m == 0: GHS_OK, no device work. An endpoint >= n: GHS_E_ARG ("edge endpoint
+ * out of range") after the sync.
+ *
+ * Diameters (ghs_forest_diameter_device): non-negative weights make two sweeps exact on a tree.
+ *   d_root_of[v]   the root of v's tree (under the index's rooting).
+ *   p              the vertex farthest from the root; among ties the smallest id.
+ *   q              the vertex farthest from p; among ties the smallest id.
+ *   d_diam[r]      for a root r: dist(p, q), the diameter of its tree. 0 for every non-root slot.
+ *   d_end_a[r], d_end_b[r]   for a root r: p and q. 0xffffffff for every non-root slot. A single-vertex
+ *                  tree has diameter 0 and both ends equal to itself.
+ *   d_ecc[v]       (may be NULL) max(dist(v, p), dist(v, q)): the distance to the farthest vertex of the tree.
+ * Each sweep is n fused distance queries and a per-tree arg-max in two steps (a 63-bit distance and an
+ * id do not fit one 64-bit key): a maximum of the distance into the root's slot, then a minimum of the
+ * id among the vertices attaining it. The eccentricities are formed whether or not d_ecc is given (in
+ * the workspace otherwise): the centre is their arg-min. One host sync.
+ * Errors, in this order, before any device work: NULL result, NULL or destroyed handle, NULL pointers
+ * (d_ecc excepted), misaligned pointers (4 bytes for root_of / end_a / end_b, 8 for wdepth / diam / ecc,
+ * 16 for the workspace): GHS_E_ARG; workspace short (ghs_forest_dist_workspace_bytes): GHS_E_NOMEM. An
+ * index over n == 0: GHS_OK, no device work, 0 trees. */
+#define GHS_DIST_WEIGHT 0u   /* sum the weights of the index's level-0 keys */
+#define GHS_DIST_HOPS   1u   /* 1 per edge: the weighted depth is the depth */
+typedef struct ghs_dist_query_result {   /* 48 bytes */
+  uint64_t queries;         /* q */
+  uint64_t connected;       /* pairs in one tree (a == b included) */
+  uint64_t disconnected;    /* pairs across two trees: q - connected */
+  uint64_t max_dist;        /* the largest finite distance; 0 when no pair is connected */
+  double   ms_total;        /* host wall time of the call */
+  uint64_t reserved;        /* 0 */
+} ghs_dist_query_result_t;
+typedef struct ghs_edge_dist_result {   /* 80 bytes */
+  uint64_t edges;           /* m */
+  uint64_t sum_dist_lo;     /* the sum of the finite distances, a 128-bit value: low word ... */
+  uint64_t sum_dist_hi;     /* ... high word (260M edges times 2^40 and more do not fit 64 bits) */
+  uint64_t sum_w;           /* the sum of the weights of the same edges */
+  uint64_t max_dist;        /* the largest finite distance */
+  uint64_t cross_edges;     /* edges whose ends lie in different trees: 0 for a spanning forest */
+  uint64_t tight_edges;     /* edges with dist == w */
+  uint32_t max_eid;         /* the smallest eid attaining max_dist; 0xffffffff when every edge is a cross edge */
+  uint32_t reserved32;      /* 0 */
+  double   ms_total;        /* host wall time of the call */
+  uint64_t reserved;        /* 0 */
+} ghs_edge_dist_result_t;
+typedef struct ghs_diameter_result {   /* 48 bytes */
+  uint64_t num_trees;       /* roots */
+  uint64_t max_diameter;    /* the largest diameter */
+  uint64_t min_ecc;         /* the smallest eccentricity in the tree of max_root: its radius */
+  uint32_t max_root;        /* the root of the tree with the largest diameter (ties: the smallest root) */
+  uint32_t center;          /* the vertex of that tree attaining min_ecc (ties: the smallest id) */
+  double   ms_total;        /* host wall time of the call */
+  uint64_t reserved;        /* 0 */
+} ghs_diameter_result_t;
+size_t ghs_forest_dist_workspace_bytes(uint32_t n, uint64_t max_depth);       /* host only, no GPU needed */
+int ghs_forest_wdepth_device(ghs_paths_t *h, uint32_t metric, uint64_t *d_wdepth /* n */, void *d_workspace,
+                             size_t workspace_bytes, void *stream);
+int ghs_forest_dist_query(ghs_paths_t *h, const uint64_t *d_wdepth, uint64_t q, const uint32_t *d_a, const uint32_t *d_b,
+                          uint64_t *d_dist /* q */, uint32_t *d_lca /* q, may be NULL */,
+                          ghs_dist_query_result_t *result, void *stream);
+int ghs_forest_edge_dist_device(ghs_paths_t *h, const uint64_t *d_wdepth, uint64_t m, const uint32_t *d_u,
+                                const uint32_t *d_v, const uint32_t *d_w, uint64_t *d_dist_by_edge /* m, may be NULL */,
+                                ghs_edge_dist_result_t *result, void *stream);
+int ghs_forest_diameter_device(ghs_paths_t *h, const uint64_t *d_wdepth, uint32_t *d_root_of /* n */,
+                               uint64_t *d_diam /* n, by root */, uint32_t *d_end_a /* n, by root */,
+                               uint32_t *d_end_b /* n, by root */, uint64_t *d_ecc /* n, may be NULL */,
+                               void *d_workspace, size_t workspace_bytes, ghs_diameter_result_t *result, void *stream);
+/* the same for host arrays and flags: copy in, root the flags (ghs_forest_root_device without pre and
+ * size), build the index and the weighted depth under `metric`, answer, copy out. dist_host: q pairs,
+ * dist and lca may each be NULL. diameter_host: n entries per array, indexed as above under the rooting
+ * at every tree's smallest vertex; each array may be NULL. The argument errors above except the
+ * alignments (and NULL u / v / w / in_mst with m > 0, NULL a / b with q > 0, an unknown metric), then
+ * GHS_E_NODEVICE without a GPU. q == 0 (dist_host) and n == 0 (diameter_host): GHS_OK, no device work.
+ * Flags that close a cycle: GHS_E_ARG ("flags are not a forest"). */
+int ghs_forest_dist_host(uint32_t n, uint64_t m, const uint32_t *u, const uint32_t *v, const uint32_t *w,
+                         const uint8_t *in_mst, uint32_t metric, uint64_t q, const uint32_t *a, const uint32_t *b,
+                         uint64_t *dist, uint32_t *lca, ghs_dist_query_result_t *result);
+int ghs_forest_diameter_host(uint32_t n, uint64_t m, const uint32_t *u, const uint32_t *v, const uint32_t *w,
+                             const uint8_t *in_mst, uint32_t metric, uint32_t *root_of, uint64_t *diam, uint32_t *end_a,
+                             uint32_t *end_b, uint64_t *ecc, ghs_diameter_result_t *result);
+
 /* device-side canonicity check: *ok = 1 iff u < v < n and (u, v) strictly ascending */
 int ghs_check_canonical(uint32_t n, uint64_t m, const uint32_t *d_u, const uint32_t *d_v, void *stream, int *ok);
 
