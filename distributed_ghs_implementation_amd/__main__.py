@@ -24,6 +24,11 @@
                    after the solve, write the forest rooted at every tree's smallest vertex: numpy
                    uint32 arrays parent, parent_eid (0xffffffff for a root), depth, pre (DFS preorder)
                    and size (subtree sizes), computed on the GPU
+    --dendrogram OUT.npz
+                   after the solve, write the single-linkage dendrogram of the forest, computed on the
+                   GPU: merge j is the j-th lightest forest edge, vertex v is node v and merge j node
+                   n + j (scipy's ids); leaf_parent per vertex, and per merge merge_eid, merge_parent,
+                   child_a, child_b, size (uint32, 0xffffffff: none) and height (its weight)
     --paths OUT.npz --pairs PAIRS.npy
                    after the solve, answer path queries on the forest on the GPU: PAIRS.npy is an
                    integer array of shape (Q, 2); OUT.npz holds a, b, eid (the heaviest edge between
@@ -155,6 +160,9 @@ def main(argv=None):
                     help="with --labels: keep forest edges of weight <= T (single linkage at distance T)")
     ap.add_argument("--rooted", type=str, default=None, metavar="OUT.npz",
                     help="write the rooted forest (parent, parent_eid, depth, pre, size: uint32) after the solve")
+    ap.add_argument("--dendrogram", type=str, default=None, metavar="OUT.npz",
+                    help="write the single-linkage dendrogram (leaf_parent, merge_eid, merge_parent, child_a, child_b, "
+                         "size, height) after the solve")
     ap.add_argument("--paths", type=str, default=None, metavar="OUT.npz",
                     help="write the path queries' answers (a, b, eid, weight, lca, hops) after the solve; needs --pairs")
     ap.add_argument("--pairs", type=str, default=None, metavar="PAIRS.npy",
@@ -281,6 +289,15 @@ def main(argv=None):
         if not args.quiet:
             print(f"Rooted forest: {rinfo['num_trees']} trees, max depth {rinfo['max_depth']}")
             print(f"Rooted forest saved to: {args.rooted}")
+    if args.dendrogram:
+        import numpy as np
+
+        from .mst import MSTResult
+        dg, dinfo = MSTResult(g, np.asarray(flags), 0, rounds, [], ms).dendrogram(return_info=True)
+        np.savez(args.dendrogram, **dg)
+        if not args.quiet:
+            print(f"Dendrogram: {dinfo['flagged_edges']} merges, {dinfo['num_trees']} trees, height {dinfo['max_height']}")
+            print(f"Dendrogram saved to: {args.dendrogram}")
     if args.paths:
         import numpy as np
 

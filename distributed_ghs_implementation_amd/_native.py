@@ -72,6 +72,7 @@ EXPORTED_SYMBOLS = (
     "ghs_forest_replace_phases",
     "ghs_forest_dist_workspace_bytes", "ghs_forest_wdepth_device", "ghs_forest_dist_query",
     "ghs_forest_edge_dist_device", "ghs_forest_diameter_device", "ghs_forest_dist_host", "ghs_forest_diameter_host",
+    "ghs_forest_dendro_workspace_bytes", "ghs_forest_dendro_device", "ghs_forest_dendro_host",
 )
 
 
@@ -214,6 +215,25 @@ class RootResult(ctypes.Structure):
         ("is_forest", ctypes.c_uint32),
         ("ms_total", ctypes.c_double),
         ("reserved", ctypes.c_uint64),
+    ]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+        d["is_forest"] = bool(d["is_forest"])
+        return d
+
+
+class DendroResult(ctypes.Structure):
+    """ghs_dendro_result_t: what ghs_forest_dendro_device / ghs_forest_dendro_host found."""
+    _fields_ = [
+        ("flagged_edges", ctypes.c_uint64),
+        ("num_trees", ctypes.c_uint64),
+        ("max_height", ctypes.c_uint64),
+        ("levels", ctypes.c_uint32),
+        ("rounds", ctypes.c_uint32),
+        ("is_forest", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+        ("ms_total", ctypes.c_double),
     ]
 
     def as_dict(self):
@@ -554,6 +574,11 @@ def load():
             "ghs_forest_diameter_device": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, sz, P(DiameterResult), vp]),
             "ghs_forest_dist_host": (i32, [u32, u64, vp, vp, vp, vp, u32, u64, vp, vp, vp, vp, P(DistQueryResult)]),
             "ghs_forest_diameter_host": (i32, [u32, u64, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, P(DiameterResult)]),
+            # ABI 10 addition: the single-linkage dendrogram (Kruskal merge tree) of the flagged forest
+            "ghs_forest_dendro_workspace_bytes": (sz, [u32, u64]),
+            "ghs_forest_dendro_device": (i32, [u32, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp,
+                                               P(DendroResult)]),
+            "ghs_forest_dendro_host": (i32, [u32, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, P(DendroResult)]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(L, name)

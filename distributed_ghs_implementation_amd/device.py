@@ -417,6 +417,11 @@ class DeviceMST:
         its smallest vertex."""
         return forest_root(self.edges, self.in_mst, order=order)
 
+    def dendrogram(self, children=True, sizes=True):
+        """`forest_dendrogram` of the engine's own flags (after `run()`): the single-linkage merge
+        order of the graph."""
+        return forest_dendrogram(self.edges, self.in_mst, children=children, sizes=sizes)
+
     def paths(self):
         """`forest_paths` of the engine's own flags (after `run()`): a PathIndex answering bottleneck
         edge / LCA / hop-count queries on the MSF."""
@@ -676,6 +681,95 @@ def forest_root(edges, in_mst, order=True):
                                                ctypes.byref(res)))
     del ws
     return RootedForest(*out), res.as_dict()
+
+
+class Dendrogram:
+    """The single-linkage dendrogram of a flagged forest (`forest_dendrogram`): int32 GPU tensors
+    holding uint32 bit patterns. n vertices, t merges; vertex v is node v, merge j (the j-th lightest
+    forest edge under (w, eid)) is node n + j, as in scipy. leaf_parent[n]: the merge that first
+    absorbs a vertex (-1: isolated); merge_eid[t]: the canonical edge of a merge; merge_parent[t]: the
+    merge that absorbs its cluster next (-1: the last merge of a tree); child_a[t] < child_b[t]: the
+    two nodes it joins; size[t]: the vertices of its cluster. child_a / child_b / size are None when
+    the call left them out. info: the fields of ghs_dendro_result_t as a dict."""
+
+    def __init__(self, n, leaf_parent, merge_eid, merge_parent, child_a, child_b, size, info=None):
+        self.n = int(n)
+        self.leaf_parent, self.merge_eid, self.merge_parent = leaf_parent, merge_eid, merge_parent
+        self.child_a, self.child_b, self.size, self.info = child_a, child_b, size, info
+
+    @property
+    def t(self):
+        return int(self.merge_eid.numel())
+
+    def heights(self, edges):
+        """The merge heights in the caller's own units, in merge order: edges.weights[merge_eid] (of
+        that tensor's dtype) for rank-mapped weights, otherwise the engine's uint32 weights as int64."""
+        eid = self.merge_eid.to(torch.int64) & 0xFFFFFFFF
+        if edges.weights is not None:
+            return edges.weights[eid]
+        return edges.w[eid].to(torch.int64) & 0xFFFFFFFF
+
+    def linkage(self, edges):
+        """scipy's linkage matrix: a numpy float64 (t, 4) array [child_a, child_b, height, size]. Needs
+        the children and the sizes, and a forest that is one tree (t == n - 1): ValueError otherwise."""
+        import numpy as np
+        if self.child_a is None or self.child_b is None or self.size is None:
+            raise ValueError("linkage needs the children and the sizes (forest_dendrogram(children=True, sizes=True))")
+        if self.info is not None and not self.info.get("is_forest", True):
+            raise ValueError("the flags close a cycle: there is no dendrogram")
+        if self.n < 1 or self.t != self.n - 1:
+            raise ValueError(f"linkage needs one tree: {self.t} merges on {self.n} vertices")
+        Z = np.empty((self.t, 4), np.float64)
+        for k, col in enumerate((self.child_a, self.child_b)):
+            Z[:, k] = (col.to(torch.int64) & 0xFFFFFFFF).cpu().numpy()
+        Z[:, 2] = self.heights(edges).cpu().numpy()
+        Z[:, 3] = (self.size.to(torch.int64) & 0xFFFFFFFF).cpu().numpy()
+        return Z
+
+
+def forest_dendrogram(edges, in_mst, children=True, sizes=True):
+    """The single-linkage dendrogram (the Kruskal merge tree) of the flagged forest on the device
+    (ghs_forest_dendro_device, csrc/dendro.hip), at any depth: nothing walks a path or a chain.
+    edges: a DeviceEdges with `u` present (a CSR-only list raises ValueError); in_mst: a uint8 / bool
+    GPU tensor of at least m flags (nonzero = in the forest), only read. More than min(m, n - 1) flags
+    raise GHSError (GHS_E_ARG); flags that close a cycle are reported as info["is_forest"] = False, and
+    the arrays are then unspecified.
+    Returns a Dendrogram (tensors trimmed to the t merges found, and .info: flagged_edges, num_trees,
+    max_height, levels, rounds, is_forest, ms_total). children=False leaves child_a / child_b out,
+    sizes=False leaves size out (None). Runs on torch's current stream; a non-canonical list raises
+    GHSError (GHS_E_NONCANON)."""
+    if edges.u is None:
+        raise ValueError("forest_dendrogram needs the COO form (u present); a CSR-only list is not supported")
+    if not isinstance(in_mst, torch.Tensor) or in_mst.dim() != 1:
+        raise ValueError("in_mst: a one-dimensional GPU tensor of flags expected")
+    if in_mst.dtype == torch.bool:
+        in_mst = in_mst.view(torch.uint8)
+    if in_mst.dtype != torch.uint8:
+        raise ValueError(f"in_mst: uint8 or bool flags expected, got {in_mst.dtype}")
+    n, m = edges.n, edges.m
+    if in_mst.numel() < m:
+        raise ValueError(f"in_mst holds {in_mst.numel()} flags, the edge list {m} edges")
+    L = _native.load()
+    _native.require_gpu()
+    if m and (not in_mst.is_cuda or in_mst.device != edges.device):
+        raise ValueError("in_mst must be on the edge list's device")
+    if m and in_mst.stride(0) != 1:
+        in_mst = in_mst.contiguous()
+    cap = min(m, max(n - 1, 0))
+    with torch.cuda.device(edges.device):
+        res = _native.DendroResult()
+        leaf = torch.empty(n, dtype=torch.int32, device=edges.device)
+        want = (True, True, children, children, sizes)
+        out = [torch.empty(cap, dtype=torch.int32, device=edges.device) if k else None for k in want]
+        ws_bytes = int(L.ghs_forest_dendro_workspace_bytes(n, m)) if m else 0
+        ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=edges.device)
+        _native.check(L.ghs_forest_dendro_device(n, m, _ptr(edges.u), _ptr(edges.v), _ptr(edges.w),
+                                                 _ptr(in_mst) if m else None, _ptr(leaf), *[_ptr(t) for t in out],
+                                                 _ptr(ws), ws_bytes, _stream(), ctypes.byref(res)))
+    del ws
+    t = int(res.flagged_edges)
+    out = [None if x is None else x[:t] for x in out]
+    return Dendrogram(n, leaf, *out, info=res.as_dict())
 
 
 class PathAnswers:

@@ -113,6 +113,38 @@ class MSTResult:
                                              *[out[k].ctypes.data for k in names], ctypes.byref(res)))
         return (out, res.as_dict()) if return_info else out
 
+    def dendrogram(self, return_info=False):
+        """The single-linkage dendrogram of the forest (ghs_forest_dendro_host, on the GPU): a dict of
+        numpy arrays. Merge j is the j-th lightest forest edge under (weight, eid); vertex v is node v
+        and merge j node n + j, as in scipy. leaf_parent (uint32, n entries): the merge that first
+        absorbs a vertex, 0xffffffff for an isolated one; per merge (t entries, uint32): merge_eid,
+        merge_parent (0xffffffff for the last merge of a tree), child_a < child_b (node ids), size
+        (vertices of the cluster); height: the merges' weights in the graph's own weights
+        (graph.weights for a rank-mapped graph, else int64). For a connected graph
+        np.column_stack([child_a, child_b, height, size]) is scipy's single linkage matrix.
+        Flags that close a cycle raise ValueError. return_info=True: (dict, the fields of
+        ghs_dendro_result_t as a dict)."""
+        g = self.graph
+        L = _native.load()
+        _native.require_gpu()
+        flags = np.ascontiguousarray(self.in_mst, dtype=np.uint8)
+        cap = max(min(g.m, g.n - 1), 0)
+        names = ("merge_eid", "merge_parent", "child_a", "child_b", "size")
+        leaf = np.empty(g.n, dtype=np.uint32)
+        out = {k: np.empty(max(cap, 1), dtype=np.uint32) for k in names}
+        res = _native.DendroResult()
+        _native.check(L.ghs_forest_dendro_host(g.n, g.m, g.u.ctypes.data, g.v.ctypes.data, g.w.ctypes.data,
+                                               flags.ctypes.data, leaf.ctypes.data,
+                                               *[out[k].ctypes.data for k in names], ctypes.byref(res)))
+        if g.n and not res.is_forest:
+            raise ValueError("the flags close a cycle: there is no dendrogram")
+        t = int(res.flagged_edges)
+        out = {k: a[:t] for k, a in out.items()}
+        eid = out["merge_eid"].astype(np.int64)
+        out["height"] = g.weights[eid] if g.weights is not None else g.w[eid].astype(np.int64)
+        out = {"leaf_parent": leaf, **out}
+        return (out, res.as_dict()) if return_info else out
+
     def paths(self, a, b, return_info=False):
         """What lies between a[i] and b[i] on the forest (ghs_forest_paths_host, on the GPU: the flags
         rooted, a jump-pointer index, one batched query). a, b: integer arrays of equal length (or

@@ -798,6 +798,79 @@ int ghs_forest_diameter_host(uint32_t n, uint64_t m, const uint32_t *u, const ui
                              const uint8_t *in_mst, uint32_t metric, uint32_t *root_of, uint64_t *diam, uint32_t *end_a,
                              uint32_t *end_b, uint64_t *ecc, ghs_diameter_result_t *result);
 
+/* ---- single-linkage dendrogram: in which order do the clusters merge? (ABI 10 addition) -----------
+ * ghs_forest_labels_device answers one cut and the path query one pair per call; this call gives the
+ * whole merge order: the Kruskal merge tree of the flagged forest T (t = |T| edges with a nonzero flag
+ * byte), scipy's linkage matrix for the engine's MSF. Merge j, 0 <= j < t, is the j-th lightest edge
+ * of T under the key (w, eid). Node ids are scipy's: vertex v is node v, merge j is node n + j.
+ *   d_leaf_parent[n]    the merge that first absorbs vertex v = the rank of v's lightest incident
+ *                       T-edge; 0xffffffff for an isolated vertex.
+ *   d_merge_eid[t]      the canonical edge id of merge j.
+ *   d_merge_parent[t]   the merge that next absorbs the cluster made by merge j; 0xffffffff for the
+ *                       last merge of a tree.
+ *   d_child_a[t], d_child_b[t]   the two node ids joined by merge j, child_a < child_b.
+ *   d_size[t]           the number of vertices of the cluster after merge j.
+ * All arrays have capacity C = min(m, n - 1); entries at index >= t are not written. d_child_a,
+ * d_child_b and d_size may be NULL, independently. Exact integers; two calls give identical bytes. For
+ * a connected graph with distinct weights [child_a, child_b, w[merge_eid], size] is
+ * scipy.cluster.hierarchy.linkage(y, 'single').
+ * A T that closes a cycle is a result, not an error: GHS_OK with is_forest = 0 and flagged_edges exact;
+ * the other fields and the arrays are then unspecified (written only in bounds). More than
+ * min(m, n - 1) flagged edges: GHS_E_ARG ("more flags than a forest can hold") after the count.
+ * Method (csrc/dendro.hip): a dendrogram is as high as a path is long, so nothing is level-synchronous
+ * in the depth of the forest or of the dendrogram. The t keys are sorted by rocPRIM; an edge is its
+ * rank from there on. A level takes supervertices and a forest of edges on them: every supervertex
+ * finds its lightest incident edge (atomicMin; at level 0 this is leaf_parent); an edge that is the
+ * lightest of an end is chosen, the others are alpha edges (at most half); the groups are the
+ * components of the chosen edges, found by pointer doubling and numbered by a scan; the alpha edges
+ * over the groups are the next level. On the way back a chosen edge e of group S hangs under the
+ * highest node among S and its ancestors in the deeper level's dendrogram that is lighter than e,
+ * found by binary lifting; a stable sort by that node lines the chosen edges up in chains, each one's
+ * parent the next. Children come from atomicMin / atomicMax into the parent's two slots, sizes and the
+ * height from doubling up the finished parents with integer atomicAdd.
+ * levels <= ceil(log2(max(n, 2))) contraction levels with an edge. rounds = the data-dependent
+ * doubling rounds: per level at most ceil(log2 nv) + 1 pointer jumps and ceil(log2 ne') + 2 lifting
+ * tables, then at most ceil(log2 t) + 3 size rounds, so rounds <= levels (2 ceil(log2 n) + 3) +
+ * ceil(log2 n) + 3 (DESIGN.md "Dendrogram"); GHS_E_ROUNDCAP past either bound is never expected.
+ * d_in_mst (m bytes, any alignment) is only read. Work is enqueued on `stream`; the call returns once
+ * *result and the arrays are final (one host sync per round and three per level).
+ * Workspace (ghs_forest_dendro_workspace_bytes, computed on the host, no GPU needed), sized by
+ * C = min(m, n - 1) possible merges, not by m: kept per level 20 B per edge of the level (+ 16 B past
+ * level 0), at most C >> l edges at level l: at most 56 B per possible merge over all levels; + a
+ * scratch that is the largest of: the key sort (16 B per possible merge + 4 B per 4096 edges of m), a
+ * level (28 B per vertex + 8 B per possible merge), an expansion (2 (ceil(log2(C / 2)) + 2) + 12 B
+ * per possible merge: the lifting tables), sizes (20 B per possible merge); + rocPRIM's sort / scan
+ * storage + 1 KiB of status.
+ * Errors, checked before any device work (so they hold on a host without GPU): result NULL,
+ * m >= 2^31, n + min(m, n - 1) > 2^32 (node ids), NULL or misaligned pointers (16 bytes for u / v / w /
+ * workspace, 4 for the six outputs): GHS_E_ARG; workspace_bytes short: GHS_E_NOMEM. n == 0: GHS_OK,
+ * nothing written. m == 0, n > 0: every leaf_parent is 0xffffffff (only that pointer is needed). A
+ * non-canonical list (ghs_check_canonical): GHS_E_NONCANON before any index is formed from it. */
+typedef struct ghs_dendro_result {   /* 48 bytes */
+  uint64_t flagged_edges;   /* t = |T| */
+  uint64_t num_trees;       /* n - t (isolated vertices included) */
+  uint64_t max_height;      /* the dendrogram's height in merges: the longest chain of parents */
+  uint32_t levels;          /* contraction levels that held an edge */
+  uint32_t rounds;          /* data-dependent doubling / jumping rounds */
+  uint32_t is_forest;       /* 1 iff T closes no cycle */
+  uint32_t reserved;        /* 0 */
+  double   ms_total;        /* host wall time of the call */
+} ghs_dendro_result_t;
+size_t ghs_forest_dendro_workspace_bytes(uint32_t n, uint64_t m);   /* host only, no GPU needed */
+int ghs_forest_dendro_device(uint32_t n, uint64_t m, const uint32_t *d_u, const uint32_t *d_v, const uint32_t *d_w,
+                             const uint8_t *d_in_mst,
+                             uint32_t *d_leaf_parent /* n */, uint32_t *d_merge_eid, uint32_t *d_merge_parent,
+                             uint32_t *d_child_a /* may be NULL */, uint32_t *d_child_b /* may be NULL */,
+                             uint32_t *d_size /* may be NULL */,
+                             void *d_workspace, size_t workspace_bytes, void *stream,
+                             ghs_dendro_result_t *result);
+/* the same for host arrays (copy in, run, copy out on the default stream; child_a, child_b and size may
+ * be NULL; nothing but leaf_parent is copied out when is_forest = 0); the argument errors above except
+ * the alignments, then GHS_E_NODEVICE without a GPU */
+int ghs_forest_dendro_host(uint32_t n, uint64_t m, const uint32_t *u, const uint32_t *v, const uint32_t *w,
+                           const uint8_t *in_mst, uint32_t *leaf_parent, uint32_t *merge_eid, uint32_t *merge_parent,
+                           uint32_t *child_a, uint32_t *child_b, uint32_t *size, ghs_dendro_result_t *result);
+
 /* device-side canonicity check: *ok = 1 iff u < v < n and (u, v) strictly ascending */
 int ghs_check_canonical(uint32_t n, uint64_t m, const uint32_t *d_u, const uint32_t *d_v, void *stream, int *ok);
 
