@@ -24,6 +24,12 @@ forest_edge_distances / forest_diameters, PathIndex.wdepth / distances / edge_di
 DeviceMST.distances / edge_distances / diameters, MSTResult.distances / edge_distances / diameters,
 CLI --distances / --pairs, --diameters, --stretch (--hops counts edges: the only metric for rank-mapped
 weights);
+the single-linkage dendrogram (the whole merge order, scipy's linkage matrix): device.forest_dendrogram,
+DeviceMST.dendrogram, MSTResult.dendrogram, CLI --dendrogram;
+HDBSCAN cluster extraction from it (the condensed tree for a min_cluster_size, stabilities, the
+excess-of-mass or leaf selection, labels with noise and membership probabilities):
+device.forest_clusters, Dendrogram.clusters, DeviceMST.clusters, MSTResult.clusters,
+CLI --clusters OUT.npz --min-cluster-size K;
 multi-GPU: distributed.DistributedMST. Float, negative and 64-bit
 weights: rank-mapped by graph.canonicalize on the host, or on the device with rank_weights=True
 (minimum_spanning_forest_edges, DeviceEdges.from_raw, canonicalize_device; device.weight_ranks).

@@ -29,6 +29,13 @@
                    GPU: merge j is the j-th lightest forest edge, vertex v is node v and merge j node
                    n + j (scipy's ids); leaf_parent per vertex, and per merge merge_eid, merge_parent,
                    child_a, child_b, size (uint32, 0xffffffff: none) and height (its weight)
+    --clusters OUT.npz --min-cluster-size K [--cluster-method eom|leaf] [--allow-single-cluster]
+                   after the solve, HDBSCAN cluster extraction from that dendrogram on the GPU (a
+                   --clusters value that is no integer is this output file): label (int32 per vertex,
+                   -1: noise; a value that parses as an integer always means K, so name a file ./123), probability, point_cluster, point_lambda, and per cluster of the
+                   condensed tree cluster_head, cluster_parent, cluster_size, cluster_birth,
+                   cluster_stability, cluster_selected, with the counts num_clusters, num_selected,
+                   num_noise, num_top, cluster_height; a forest edge of weight 0 is an error
     --paths OUT.npz --pairs PAIRS.npy
                    after the solve, answer path queries on the forest on the GPU: PAIRS.npy is an
                    integer array of shape (Q, 2); OUT.npz holds a, b, eid (the heaviest edge between
@@ -155,7 +162,16 @@ def main(argv=None):
     ap.add_argument("--check-result", type=str, default=None, help="verify an existing result JSON only")
     ap.add_argument("--labels", type=str, default=None, metavar="OUT.npy",
                     help="write the vertices' cluster labels (uint32 .npy) after the solve")
-    ap.add_argument("--clusters", type=int, default=None, help="with --labels: single linkage into K clusters")
+    ap.add_argument("--clusters", type=str, default=None, metavar="K | OUT.npz",
+                    help="an integer, with --labels: single linkage into K clusters; anything else is a file name: "
+                         "write the HDBSCAN clusters of the forest's dendrogram (needs --min-cluster-size). A value "
+                         "that parses as an integer always means K: name an output file ./123, not 123")
+    ap.add_argument("--min-cluster-size", type=int, default=None, metavar="K",
+                    help="with --clusters OUT.npz: the smallest cluster HDBSCAN keeps (>= 2)")
+    ap.add_argument("--cluster-method", choices=["eom", "leaf"], default="eom",
+                    help="with --clusters OUT.npz: excess of mass (default) or the leaves of the condensed tree")
+    ap.add_argument("--allow-single-cluster", action="store_true",
+                    help="with --clusters OUT.npz: a lone tree top may be selected")
     ap.add_argument("--max-weight", type=float, default=None,
                     help="with --labels: keep forest edges of weight <= T (single linkage at distance T)")
     ap.add_argument("--rooted", type=str, default=None, metavar="OUT.npz",
@@ -181,6 +197,16 @@ def main(argv=None):
     ap.add_argument("--scale", type=int, default=16, help="R-MAT scale (2^scale vertices) / grid side k")
     ap.add_argument("--seed", type=int, default=1, help="generator seed (weights: seed + 1)")
     args = ap.parse_args(argv)
+    args.hdbscan = None
+    if args.clusters is not None:
+        try:
+            args.clusters = int(args.clusters)
+        except ValueError:
+            args.hdbscan, args.clusters = args.clusters, None
+    if args.hdbscan is not None and (args.min_cluster_size is None or args.min_cluster_size < 2):
+        ap.error("--clusters OUT.npz needs --min-cluster-size K with K >= 2")
+    if args.hdbscan is None and args.min_cluster_size is not None:
+        ap.error("--min-cluster-size needs --clusters OUT.npz")
     if args.clusters is not None and args.max_weight is not None:
         ap.error("--clusters and --max-weight exclude each other")
     if (args.clusters is not None or args.max_weight is not None) and not args.labels:
@@ -298,6 +324,18 @@ def main(argv=None):
         if not args.quiet:
             print(f"Dendrogram: {dinfo['flagged_edges']} merges, {dinfo['num_trees']} trees, height {dinfo['max_height']}")
             print(f"Dendrogram saved to: {args.dendrogram}")
+    if args.hdbscan:
+        import numpy as np
+
+        from .mst import MSTResult
+        cl, cinfo = MSTResult(g, np.asarray(flags), 0, rounds, [], ms).clusters(
+            min_cluster_size=args.min_cluster_size, method=args.cluster_method,
+            allow_single_cluster=args.allow_single_cluster, return_info=True)
+        np.savez(args.hdbscan, **cl, **{k: np.asarray(v) for k, v in cinfo.items() if k != "ms_total"})
+        if not args.quiet:
+            print(f"Clusters: {cinfo['num_selected']} selected of {cinfo['num_clusters']} in the condensed tree "
+                  f"(height {cinfo['cluster_height']}), {cinfo['num_noise']} noise vertices")
+            print(f"Clusters saved to: {args.hdbscan}")
     if args.paths:
         import numpy as np
 

@@ -73,6 +73,8 @@ EXPORTED_SYMBOLS = (
     "ghs_forest_dist_workspace_bytes", "ghs_forest_wdepth_device", "ghs_forest_dist_query",
     "ghs_forest_edge_dist_device", "ghs_forest_diameter_device", "ghs_forest_dist_host", "ghs_forest_diameter_host",
     "ghs_forest_dendro_workspace_bytes", "ghs_forest_dendro_device", "ghs_forest_dendro_host",
+    "ghs_forest_cluster_workspace_bytes", "ghs_forest_cluster_capacity", "ghs_forest_cluster_device",
+    "ghs_forest_cluster_host",
 )
 
 
@@ -240,6 +242,38 @@ class DendroResult(ctypes.Structure):
         d = {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
         d["is_forest"] = bool(d["is_forest"])
         return d
+
+
+GHS_CLUSTER_ALLOW_SINGLE = 1
+GHS_CLUSTER_LEAF = 2
+
+
+class ClusterResult(ctypes.Structure):
+    """ghs_cluster_result_t: what ghs_forest_cluster_device / ghs_forest_cluster_host found."""
+    _fields_ = [
+        ("num_clusters", ctypes.c_uint32),
+        ("num_selected", ctypes.c_uint32),
+        ("num_noise", ctypes.c_uint32),
+        ("num_top", ctypes.c_uint32),
+        ("cluster_height", ctypes.c_uint32),
+        ("rounds", ctypes.c_uint32),
+        ("select_launches", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+        ("ms_total", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+def cluster_args(min_cluster_size, method, allow_single_cluster):
+    """(min_cluster_size, flags) of the cluster entry points; ValueError for what they would refuse."""
+    mcs = int(min_cluster_size)
+    if mcs < 2:
+        raise ValueError(f"min_cluster_size must be >= 2, got {min_cluster_size}")
+    if method not in ("eom", "leaf"):
+        raise ValueError(f"method: 'eom' or 'leaf' expected, got {method!r}")
+    return mcs, (GHS_CLUSTER_LEAF if method == "leaf" else 0) | (GHS_CLUSTER_ALLOW_SINGLE if allow_single_cluster else 0)
 
 
 class PathsResult(ctypes.Structure):
@@ -579,6 +613,12 @@ def load():
             "ghs_forest_dendro_device": (i32, [u32, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp,
                                                P(DendroResult)]),
             "ghs_forest_dendro_host": (i32, [u32, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, P(DendroResult)]),
+            # ABI 10 addition: HDBSCAN cluster extraction from a dendrogram and one height per merge
+            "ghs_forest_cluster_workspace_bytes": (sz, [u32, u64, u32]),
+            "ghs_forest_cluster_capacity": (u64, [u32, u64, u32]),
+            "ghs_forest_cluster_device": (i32, [u32, u64] + [vp] * 6 + [u32, u32] + [vp] * 10 + [vp, sz, vp,
+                                                P(ClusterResult)]),
+            "ghs_forest_cluster_host": (i32, [u32, u64] + [vp] * 6 + [u32, u32] + [vp] * 10 + [P(ClusterResult)]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(L, name)

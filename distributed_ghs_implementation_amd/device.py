@@ -422,6 +422,12 @@ class DeviceMST:
         order of the graph."""
         return forest_dendrogram(self.edges, self.in_mst, children=children, sizes=sizes)
 
+    def clusters(self, min_cluster_size=5, method="eom", allow_single_cluster=False, probabilities=True):
+        """HDBSCAN clusters of the engine's own forest (after `run()`): `dendrogram()`, then
+        `forest_clusters` with the merge heights in the edge list's own weights."""
+        return self.dendrogram().clusters(self.edges, min_cluster_size=min_cluster_size, method=method,
+                                          allow_single_cluster=allow_single_cluster, probabilities=probabilities)
+
     def paths(self):
         """`forest_paths` of the engine's own flags (after `run()`): a PathIndex answering bottleneck
         edge / LCA / hop-count queries on the MSF."""
@@ -726,6 +732,12 @@ class Dendrogram:
         Z[:, 3] = (self.size.to(torch.int64) & 0xFFFFFFFF).cpu().numpy()
         return Z
 
+    def clusters(self, edges, min_cluster_size=5, method="eom", allow_single_cluster=False, probabilities=True):
+        """`forest_clusters` of this dendrogram with the heights taken from `heights(edges)`: the HDBSCAN
+        condensed tree, stabilities, selection, labels and probabilities, in the caller's own units."""
+        return forest_clusters(self, edges=edges, min_cluster_size=min_cluster_size, method=method,
+                               allow_single_cluster=allow_single_cluster, probabilities=probabilities)
+
 
 def forest_dendrogram(edges, in_mst, children=True, sizes=True):
     """The single-linkage dendrogram (the Kruskal merge tree) of the flagged forest on the device
@@ -770,6 +782,108 @@ def forest_dendrogram(edges, in_mst, children=True, sizes=True):
     t = int(res.flagged_edges)
     out = [None if x is None else x[:t] for x in out]
     return Dendrogram(n, leaf, *out, info=res.as_dict())
+
+
+class Clusters:
+    """What `forest_clusters` found (ghs_forest_cluster_device), as GPU tensors. Per vertex (n entries):
+    label (int32, -1: noise), probability (float64, None when left out), point_cluster (int32 holding
+    uint32 bits, -1: none) and point_lambda (float64). Per cluster, trimmed to the K clusters found:
+    cluster_head (the head merge), cluster_parent (-1: a tree top), cluster_size, cluster_birth,
+    cluster_stability (float64) and cluster_selected (uint8). Cluster ids run by head merge index
+    descending: a parent has a smaller id than its children. info: the fields of ghs_cluster_result_t."""
+
+    def __init__(self, n, label, probability, point_cluster, point_lambda, cluster_head, cluster_parent, cluster_size,
+                 cluster_birth, cluster_stability, cluster_selected, info=None):
+        self.n = int(n)
+        self.label, self.probability = label, probability
+        self.point_cluster, self.point_lambda = point_cluster, point_lambda
+        self.cluster_head, self.cluster_parent, self.cluster_size = cluster_head, cluster_parent, cluster_size
+        self.cluster_birth, self.cluster_stability, self.cluster_selected = cluster_birth, cluster_stability, cluster_selected
+        self.info = info
+
+    @property
+    def num_clusters(self):
+        return int(self.cluster_head.numel())
+
+    def condensed_tree(self):
+        """The condensed tree as a numpy structured array of (parent, child, lambda_val, child_size)
+        rows: one row per cluster with a parent (child = n + its id, lambda_val = its birth), then one
+        per vertex with a cluster (child = the vertex, child_size 1). Parents are n + cluster id."""
+        import numpy as np
+        dt = np.dtype([("parent", np.int64), ("child", np.int64), ("lambda_val", np.float64), ("child_size", np.int64)])
+        cpar = self.cluster_parent.cpu().numpy().astype(np.int64)
+        kids = np.nonzero(cpar >= 0)[0]
+        pc = self.point_cluster.cpu().numpy().astype(np.int64)
+        pts = np.nonzero(pc >= 0)[0]
+        rows = np.empty(len(kids) + len(pts), dt)
+        k = len(kids)
+        rows["parent"][:k] = self.n + cpar[kids]
+        rows["child"][:k] = self.n + kids
+        rows["lambda_val"][:k] = self.cluster_birth.cpu().numpy()[kids]
+        rows["child_size"][:k] = (self.cluster_size.to(torch.int64) & 0xFFFFFFFF).cpu().numpy()[kids]
+        rows["parent"][k:] = self.n + pc[pts]
+        rows["child"][k:] = pts
+        rows["lambda_val"][k:] = self.point_lambda.cpu().numpy()[pts]
+        rows["child_size"][k:] = 1
+        return rows
+
+
+def forest_clusters(dendrogram, edges=None, heights=None, min_cluster_size=5, method="eom", allow_single_cluster=False,
+                    probabilities=True):
+    """HDBSCAN cluster extraction from a `Dendrogram` on the device (ghs_forest_cluster_device,
+    csrc/cluster.hip): the condensed tree for min_cluster_size, every cluster's stability, the
+    excess-of-mass (method="eom") or leaf (method="leaf") selection, and per vertex a label, noise (-1)
+    and a membership probability; scikit-learn's rule for its defaults. The heights, one per merge in
+    merge order, are `dendrogram.heights(edges)` (give `edges`) or a tensor / array of t numbers (give
+    `heights`), cast to float64: exactly one of the two. They must be finite, > 0 and non-decreasing: a
+    zero height (an integer weight 0, duplicate points) raises GHSError (GHS_E_ARG), as does any
+    malformed dendrogram. Several trees are treated as joined at infinite distance; a tree with fewer
+    than min_cluster_size vertices is noise. ValueError for a dendrogram without children or sizes, for
+    one whose flags closed a cycle, and for min_cluster_size < 2. probabilities=False leaves them out.
+    Returns a `Clusters`. Runs on torch's current stream."""
+    if (edges is None) == (heights is None):
+        raise ValueError("forest_clusters needs exactly one of edges= (heights from the dendrogram) and heights=")
+    if dendrogram.child_a is None or dendrogram.child_b is None or dendrogram.size is None:
+        raise ValueError("forest_clusters needs the children and the sizes (forest_dendrogram(children=True, sizes=True))")
+    if dendrogram.info is not None and not dendrogram.info.get("is_forest", True):
+        raise ValueError("the flags close a cycle: there is no dendrogram")
+    mcs, flags = _native.cluster_args(min_cluster_size, method, allow_single_cluster)
+    n, t = dendrogram.n, dendrogram.t
+    L = _native.load()
+    _native.require_gpu()
+    dev = dendrogram.leaf_parent.device
+    if heights is None:
+        heights = dendrogram.heights(edges)
+    if not isinstance(heights, torch.Tensor):
+        import numpy as np
+        heights = torch.from_numpy(np.ascontiguousarray(np.asarray(heights, dtype=np.float64)))
+    h = heights.to(device=dev, dtype=torch.float64).contiguous()
+    if h.dim() != 1 or h.numel() != t:
+        raise ValueError(f"heights: {t} numbers expected, one per merge")
+    cap = int(L.ghs_forest_cluster_capacity(n, t, mcs))
+    with torch.cuda.device(dev):
+        res = _native.ClusterResult()
+        i32 = dict(dtype=torch.int32, device=dev)
+        f64 = dict(dtype=torch.float64, device=dev)
+        label = torch.empty(n, **i32)
+        prob = torch.empty(n, **f64) if probabilities else None
+        pc = torch.empty(n, **i32)
+        pl = torch.empty(n, **f64)
+        c_head, c_par, c_size = (torch.empty(cap, **i32) for _ in range(3))
+        c_birth, c_stab = (torch.empty(cap, **f64) for _ in range(2))
+        c_sel = torch.empty(cap, dtype=torch.uint8, device=dev)
+        ws_bytes = int(L.ghs_forest_cluster_workspace_bytes(n, t, mcs))
+        ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=dev)
+        ins = [t_.contiguous() for t_ in (dendrogram.leaf_parent, dendrogram.merge_parent, dendrogram.child_a,
+                                          dendrogram.child_b, dendrogram.size)]
+        _native.check(L.ghs_forest_cluster_device(n, t, *[_ptr(x) for x in ins], _ptr(h), mcs, flags, _ptr(label),
+                                                  _ptr(prob), _ptr(pc), _ptr(pl), _ptr(c_head), _ptr(c_par),
+                                                  _ptr(c_size), _ptr(c_birth), _ptr(c_stab), _ptr(c_sel), _ptr(ws),
+                                                  ws_bytes, _stream(), ctypes.byref(res)))
+    del ws
+    K = int(res.num_clusters)
+    return Clusters(n, label, prob, pc, pl, c_head[:K], c_par[:K], c_size[:K], c_birth[:K], c_stab[:K], c_sel[:K],
+                    info=res.as_dict())
 
 
 class PathAnswers:

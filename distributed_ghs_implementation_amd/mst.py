@@ -145,6 +145,35 @@ class MSTResult:
         out = {"leaf_parent": leaf, **out}
         return (out, res.as_dict()) if return_info else out
 
+    def clusters(self, min_cluster_size=5, method="eom", allow_single_cluster=False, return_info=False):
+        """HDBSCAN cluster extraction from the forest's dendrogram (`dendrogram()`, then
+        ghs_forest_cluster_host, on the GPU), the merge heights in the graph's own weights as float64:
+        a dict of numpy arrays. Per vertex: label (int32, -1: noise), probability (float64),
+        point_cluster (uint32, 0xffffffff: none), point_lambda; per cluster (K entries, ids by head
+        merge index descending): cluster_head, cluster_parent (0xffffffff: a tree top), cluster_size,
+        cluster_birth, cluster_stability, cluster_selected (uint8). method: "eom" or "leaf". A weight
+        of 0 raises GHSError (GHS_E_ARG): lambda = 1 / height would be infinite. return_info=True:
+        (dict, the fields of ghs_cluster_result_t as a dict)."""
+        mcs, flags = _native.cluster_args(min_cluster_size, method, allow_single_cluster)
+        dg = self.dendrogram()
+        n, t = self.graph.n, len(dg["merge_parent"])
+        L = _native.load()
+        ins = [np.ascontiguousarray(dg[k], dtype=np.uint32) for k in ("leaf_parent", "merge_parent", "child_a", "child_b",
+                                                                      "size")]
+        height = np.ascontiguousarray(dg["height"], dtype=np.float64)
+        cap = max(int(L.ghs_forest_cluster_capacity(n, t, mcs)), 1)
+        out = {"label": np.empty(n, np.int32), "probability": np.empty(n, np.float64),
+               "point_cluster": np.empty(n, np.uint32), "point_lambda": np.empty(n, np.float64),
+               "cluster_head": np.empty(cap, np.uint32), "cluster_parent": np.empty(cap, np.uint32),
+               "cluster_size": np.empty(cap, np.uint32), "cluster_birth": np.empty(cap, np.float64),
+               "cluster_stability": np.empty(cap, np.float64), "cluster_selected": np.empty(cap, np.uint8)}
+        res = _native.ClusterResult()
+        _native.check(L.ghs_forest_cluster_host(n, t, *[a.ctypes.data for a in ins], height.ctypes.data, mcs, flags,
+                                                *[a.ctypes.data for a in out.values()], ctypes.byref(res)))
+        K = int(res.num_clusters)
+        out = {k: (a[:K] if k.startswith("cluster_") else a) for k, a in out.items()}
+        return (out, res.as_dict()) if return_info else out
+
     def paths(self, a, b, return_info=False):
         """What lies between a[i] and b[i] on the forest (ghs_forest_paths_host, on the GPU: the flags
         rooted, a jump-pointer index, one batched query). a, b: integer arrays of equal length (or

@@ -871,6 +871,92 @@ int ghs_forest_dendro_host(uint32_t n, uint64_t m, const uint32_t *u, const uint
                            const uint8_t *in_mst, uint32_t *leaf_parent, uint32_t *merge_eid, uint32_t *merge_parent,
                            uint32_t *child_a, uint32_t *child_b, uint32_t *size, ghs_dendro_result_t *result);
 
+/* ---- HDBSCAN cluster extraction from the dendrogram (ABI 10 addition) ----------------------------------
+ * The back half of HDBSCAN on a single-linkage dendrogram: the condensed tree for a min_cluster_size,
+ * every cluster's stability, the excess-of-mass (or leaf) selection, and per vertex a label, noise (-1)
+ * and a membership probability; scikit-learn's rule for its defaults (allow_single_cluster=False,
+ * cluster_selection_epsilon=0, no max_cluster_size). Its special labelling of points that fall straight
+ * out of a selected root under allow_single_cluster=True is not copied.
+ * Input: a dendrogram as ghs_forest_dendro_device writes it (n, t, d_leaf_parent[n], d_merge_parent[t],
+ * d_child_a[t], d_child_b[t], d_size[t]) and d_height[t]: one float64 height per merge, in merge order,
+ * in the caller's own units. No edge list. Heights must be finite, > 0 and non-decreasing: a zero
+ * height (an integer weight 0, duplicate points) is an error (GHS_E_ARG), not an infinite lambda.
+ * Semantics, mcs = min_cluster_size >= 2, a vertex has size 1, lambda(j) = 1.0 / height[j] (IEEE):
+ *   merge j is a true split iff both children have size >= mcs; a merge with size >= mcs is a cluster
+ *   head iff it is the last merge of its tree or its parent is a true split. Clusters are the heads,
+ *   numbered 0 .. K-1 by head merge index DESCENDING (a parent has a smaller id than its children);
+ *   K <= cap = min(t, 2 floor(n / mcs)) = ghs_forest_cluster_capacity, the capacity of every cluster
+ *   array; entries at index >= K are not written.
+ *   d_cluster_head[c], d_cluster_parent[c] (0xffffffff: a tree top), d_cluster_size[c] = size[head],
+ *   d_cluster_birth[c] = lambda(merge_parent[head]), 0.0 for a tree top: the trees of a forest are
+ *   joined at infinite distance. A tree with < mcs vertices and an isolated vertex are noise.
+ *   A vertex's anchor is its first ancestor merge with size >= mcs; d_point_cluster[v] = the cluster of
+ *   the nearest ancestor-or-self head of the anchor (0xffffffff: none), d_point_lambda[v] =
+ *   lambda(anchor) (0.0: none).
+ *   stability(C) = sum over v with point_cluster C of (point_lambda[v] - birth(C))
+ *                + sum over child clusters D of size(D) (birth(D) - birth(C)).
+ *   EOM, bottom-up, s = the sum of best over the children (0 for a leaf): a tree top when it is the only
+ *   one (num_top == 1) and GHS_CLUSTER_ALLOW_SINGLE is off is not chosen, best = s; else a leaf is
+ *   chosen; else s > stability(C): best = s; else C is chosen, best = stability(C). GHS_CLUSTER_LEAF:
+ *   the clusters without children are chosen (the lone-top rule applies the same). A cluster is selected
+ *   iff it is chosen and no ancestor is. Selected clusters in id order are the labels 0 .. S-1;
+ *   d_label[v] = the nearest selected ancestor-or-self of point_cluster[v], else -1.
+ *   d_probability[v] = min(point_lambda[v], M) / M, M = the maximum over the selected cluster's own rows
+ *   (the point_lambda of its own vertices, the birth of its child clusters); 1.0 if M == 0; 0.0 for noise.
+ * d_probability and d_point_lambda may be NULL. Stabilities are summed in a fixed order (no floating-point
+ * atomics): two calls give identical bytes in every array.
+ * Validation, on the device, before anything follows a pointer: leaf_parent[v] is none or < t;
+ * merge_parent[j] is none or j < merge_parent[j] < t; child_a[j] < child_b[j] < n + j; each child's parent
+ * pointer is j; exactly 2 t nodes have a parent; size[j] is the sum of its children's sizes; the heights
+ * as above. What passes is acyclic; anything else: GHS_E_ARG, nothing indexed out of bounds.
+ * Method (csrc/cluster.hip): heads and anchors by one fused pointer doubling over merge_parent
+ * (<= ceil(log2 t) + 1 rounds); cluster ids by a scan of the head flags; the vertices' lambdas sorted by
+ * cluster (stable rocPRIM radix sort) and each segment summed by one wave (a block past 4096 rows) in a
+ * fixed order; the EOM sweep over frontiers, synchronous in the condensed tree's height H_c only, one
+ * launch per level while a frontier is wider than 1024 clusters and one single-workgroup launch for all
+ * the remaining levels: select_launches <= min(H_c, ceil(K / 2048)) + 2; the topmost chosen ancestor by
+ * pointer doubling over cluster_parent (<= ceil(log2 K) + 1 rounds). rounds counts both doublings.
+ * Workspace (ghs_forest_cluster_workspace_bytes; it asks rocPRIM for its sort / scan storage, and that
+ * query answers 0 on a host without a GPU: take the size on the machine that runs the call): 16 B per merge + 24 B per vertex + 84 B per
+ * cluster of capacity + rocPRIM's sort / scan storage + 1 KiB of status.
+ * Errors, checked before any device work (so they hold on a host without GPU): result NULL,
+ * min_cluster_size < 2, unknown flags, n + t > 2^32 (node ids), NULL or misaligned pointers (4 bytes for
+ * the 32-bit arrays, 8 for the float64 arrays, 16 for the workspace): GHS_E_ARG; workspace_bytes short:
+ * GHS_E_NOMEM. n == 0: GHS_OK, nothing written. t == 0 (only label and point_cluster are needed) or
+ * cap == 0: every vertex is noise, K = 0. One host sync per doubling round and per sweep launch. */
+#define GHS_CLUSTER_ALLOW_SINGLE 1u   /* a lone tree top may be selected (allow_single_cluster) */
+#define GHS_CLUSTER_LEAF 2u           /* cluster_selection_method = "leaf" instead of "eom" */
+typedef struct ghs_cluster_result {   /* 40 bytes */
+  uint32_t num_clusters;    /* K: clusters of the condensed tree */
+  uint32_t num_selected;    /* S: labels are 0 .. S-1 */
+  uint32_t num_noise;       /* vertices with label -1 */
+  uint32_t num_top;         /* tree tops with >= min_cluster_size vertices */
+  uint32_t cluster_height;  /* H_c: levels of the condensed tree (a leaf cluster alone: 1) */
+  uint32_t rounds;          /* data-dependent doubling rounds (heads / anchors, selected ancestors) */
+  uint32_t select_launches; /* launches of the selection sweep, the first frontier's included */
+  uint32_t reserved;        /* 0 */
+  double   ms_total;        /* host wall time of the call */
+} ghs_cluster_result_t;
+size_t ghs_forest_cluster_workspace_bytes(uint32_t n, uint64_t t, uint32_t min_cluster_size);  /* no device work */
+uint64_t ghs_forest_cluster_capacity(uint32_t n, uint64_t t, uint32_t min_cluster_size);       /* host only */
+int ghs_forest_cluster_device(uint32_t n, uint64_t t, const uint32_t *d_leaf_parent, const uint32_t *d_merge_parent,
+                              const uint32_t *d_child_a, const uint32_t *d_child_b, const uint32_t *d_size,
+                              const double *d_height, uint32_t min_cluster_size, uint32_t flags,
+                              int32_t *d_label /* n */, double *d_probability /* n, may be NULL */,
+                              uint32_t *d_point_cluster /* n */, double *d_point_lambda /* n, may be NULL */,
+                              uint32_t *d_cluster_head /* cap */, uint32_t *d_cluster_parent, uint32_t *d_cluster_size,
+                              double *d_cluster_birth, double *d_cluster_stability, uint8_t *d_cluster_selected,
+                              void *d_workspace, size_t workspace_bytes, void *stream,
+                              ghs_cluster_result_t *result);
+/* the same for host arrays (copy in, run, copy out on the default stream); the argument errors above
+ * except the alignments, then GHS_E_NODEVICE without a GPU */
+int ghs_forest_cluster_host(uint32_t n, uint64_t t, const uint32_t *leaf_parent, const uint32_t *merge_parent,
+                            const uint32_t *child_a, const uint32_t *child_b, const uint32_t *size, const double *height,
+                            uint32_t min_cluster_size, uint32_t flags, int32_t *label, double *probability,
+                            uint32_t *point_cluster, double *point_lambda, uint32_t *cluster_head, uint32_t *cluster_parent,
+                            uint32_t *cluster_size, double *cluster_birth, double *cluster_stability,
+                            uint8_t *cluster_selected, ghs_cluster_result_t *result);
+
 /* device-side canonicity check: *ok = 1 iff u < v < n and (u, v) strictly ascending */
 int ghs_check_canonical(uint32_t n, uint64_t m, const uint32_t *d_u, const uint32_t *d_v, void *stream, int *ok);
 
