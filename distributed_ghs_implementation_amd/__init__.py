@@ -30,17 +30,21 @@ HDBSCAN cluster extraction from it (the condensed tree for a min_cluster_size, s
 excess-of-mass or leaf selection, labels with noise and membership probabilities):
 device.forest_clusters, Dendrogram.clusters, DeviceMST.clusters, MSTResult.clusters,
 CLI --clusters OUT.npz --min-cluster-size K;
+the weights HDBSCAN wants (core distances: the min_samples-th smallest weight at every vertex; mutual
+reachability: max(core[u], core[v], w) on every edge) and HDBSCAN end to end on a k-NN graph or a
+sparse distance matrix: device.mutual_reachability, DeviceEdges.mutual_reachability, device.hdbscan,
+DeviceEdges.hdbscan, mst.hdbscan_edges, CLI --mutual-reachability OUT.npz, --hdbscan OUT.npz;
 multi-GPU: distributed.DistributedMST. Float, negative and 64-bit
 weights: rank-mapped by graph.canonicalize on the host, or on the device with rank_weights=True
 (minimum_spanning_forest_edges, DeviceEdges.from_raw, canonicalize_device; device.weight_ranks).
 """
 from .graph import (CanonicalGraph, canonicalize, read_graph_dir, read_mstbin, write_graph_dir, write_mstbin,
                     write_result)
-from .mst import (GHSAlgorithm, MSTResult, minimum_spanning_forest, minimum_spanning_forest_batch,
+from .mst import (GHSAlgorithm, MSTResult, hdbscan_edges, minimum_spanning_forest, minimum_spanning_forest_batch,
                   minimum_spanning_forest_edges)
 
 __all__ = [
     "CanonicalGraph", "canonicalize", "read_graph_dir", "read_mstbin", "write_graph_dir", "write_mstbin",
     "write_result", "GHSAlgorithm", "MSTResult", "minimum_spanning_forest", "minimum_spanning_forest_batch",
-    "minimum_spanning_forest_edges",
+    "minimum_spanning_forest_edges", "hdbscan_edges",
 ]

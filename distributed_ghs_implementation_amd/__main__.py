@@ -36,6 +36,18 @@
                    condensed tree cluster_head, cluster_parent, cluster_size, cluster_birth,
                    cluster_stability, cluster_selected, with the counts num_clusters, num_selected,
                    num_noise, num_top, cluster_height; a forest edge of weight 0 is an error
+    --mutual-reachability OUT.npz [--min-samples K] [--short-rows error|clamp]
+                   the weights HDBSCAN wants, of the graph's own edges, on the GPU: core (per vertex the
+                   K-th smallest weight among its edges, default K = 5) and w (per canonical edge
+                   max(core[u], core[v], w)), with the counts short_rows, isolated, raised_edges,
+                   max_degree, block_rows, grid_rows, k; a vertex with fewer than K edges is an error
+                   unless --short-rows clamp
+    --hdbscan OUT.npz [--min-samples K] [--min-cluster-size K] [--cluster-method eom|leaf]
+              [--allow-single-cluster] [--short-rows error|clamp]
+                   HDBSCAN of the graph's own edges (a k-NN graph, a sparse distance matrix) end to end
+                   on the GPU: mutual reachability, the solve on those weights, the dendrogram, the
+                   clusters; the arrays of --clusters OUT.npz plus core and in_mst (the flags of the
+                   mutual-reachability forest); --min-cluster-size defaults to 5, --min-samples to it
     --paths OUT.npz --pairs PAIRS.npy
                    after the solve, answer path queries on the forest on the GPU: PAIRS.npy is an
                    integer array of shape (Q, 2); OUT.npz holds a, b, eid (the heaviest edge between
@@ -172,6 +184,18 @@ def main(argv=None):
                     help="with --clusters OUT.npz: excess of mass (default) or the leaves of the condensed tree")
     ap.add_argument("--allow-single-cluster", action="store_true",
                     help="with --clusters OUT.npz: a lone tree top may be selected")
+    ap.add_argument("--hdbscan", type=str, default=None, metavar="OUT.npz",
+                    help="write HDBSCAN of the graph's own edges (mutual reachability, the solve on it, the clusters); "
+                         "takes --min-samples, --min-cluster-size (default 5), --cluster-method, --allow-single-cluster, "
+                         "--short-rows")
+    ap.add_argument("--mutual-reachability", type=str, default=None, metavar="OUT.npz",
+                    help="write the core distances (core) and the mutual-reachability weights (w) of the graph's edges")
+    ap.add_argument("--min-samples", type=int, default=None, metavar="K",
+                    help="with --hdbscan / --mutual-reachability: the neighbour whose distance is the core distance "
+                         "(default: --min-cluster-size with --hdbscan, 5 with --mutual-reachability)")
+    ap.add_argument("--short-rows", choices=["error", "clamp"], default="error",
+                    help="with --hdbscan / --mutual-reachability: a vertex with fewer than --min-samples edges is an "
+                         "error (default) or takes its largest weight")
     ap.add_argument("--max-weight", type=float, default=None,
                     help="with --labels: keep forest edges of weight <= T (single linkage at distance T)")
     ap.add_argument("--rooted", type=str, default=None, metavar="OUT.npz",
@@ -197,16 +221,22 @@ def main(argv=None):
     ap.add_argument("--scale", type=int, default=16, help="R-MAT scale (2^scale vertices) / grid side k")
     ap.add_argument("--seed", type=int, default=1, help="generator seed (weights: seed + 1)")
     args = ap.parse_args(argv)
-    args.hdbscan = None
+    args.cluster_out = None
     if args.clusters is not None:
         try:
             args.clusters = int(args.clusters)
         except ValueError:
-            args.hdbscan, args.clusters = args.clusters, None
-    if args.hdbscan is not None and (args.min_cluster_size is None or args.min_cluster_size < 2):
+            args.cluster_out, args.clusters = args.clusters, None
+    if args.cluster_out is not None and (args.min_cluster_size is None or args.min_cluster_size < 2):
         ap.error("--clusters OUT.npz needs --min-cluster-size K with K >= 2")
-    if args.hdbscan is None and args.min_cluster_size is not None:
+    if args.cluster_out is None and args.hdbscan is None and args.min_cluster_size is not None:
         ap.error("--min-cluster-size needs --clusters OUT.npz")
+    if args.hdbscan is not None and args.min_cluster_size is not None and args.min_cluster_size < 2:
+        ap.error("--hdbscan OUT.npz takes --min-cluster-size K with K >= 2")
+    if args.min_samples is not None and args.hdbscan is None and args.mutual_reachability is None:
+        ap.error("--min-samples needs --hdbscan OUT.npz or --mutual-reachability OUT.npz")
+    if args.min_samples is not None and args.min_samples < 1:
+        ap.error("--min-samples K needs K >= 1")
     if args.clusters is not None and args.max_weight is not None:
         ap.error("--clusters and --max-weight exclude each other")
     if (args.clusters is not None or args.max_weight is not None) and not args.labels:
@@ -324,18 +354,53 @@ def main(argv=None):
         if not args.quiet:
             print(f"Dendrogram: {dinfo['flagged_edges']} merges, {dinfo['num_trees']} trees, height {dinfo['max_height']}")
             print(f"Dendrogram saved to: {args.dendrogram}")
-    if args.hdbscan:
+    if args.cluster_out:
         import numpy as np
 
         from .mst import MSTResult
         cl, cinfo = MSTResult(g, np.asarray(flags), 0, rounds, [], ms).clusters(
             min_cluster_size=args.min_cluster_size, method=args.cluster_method,
             allow_single_cluster=args.allow_single_cluster, return_info=True)
-        np.savez(args.hdbscan, **cl, **{k: np.asarray(v) for k, v in cinfo.items() if k != "ms_total"})
+        np.savez(args.cluster_out, **cl, **{k: np.asarray(v) for k, v in cinfo.items() if k != "ms_total"})
         if not args.quiet:
             print(f"Clusters: {cinfo['num_selected']} selected of {cinfo['num_clusters']} in the condensed tree "
                   f"(height {cinfo['cluster_height']}), {cinfo['num_noise']} noise vertices")
-            print(f"Clusters saved to: {args.hdbscan}")
+            print(f"Clusters saved to: {args.cluster_out}")
+    if args.mutual_reachability or args.hdbscan:
+        import numpy as np
+        import torch
+
+        from .device import DeviceEdges, hdbscan, mutual_reachability
+        de = DeviceEdges.from_host(g)
+        if g.weights is not None:
+            de.weights = torch.from_numpy(np.ascontiguousarray(g.weights)).to(de.device)
+        if args.mutual_reachability:
+            mr = mutual_reachability(de, min_samples=5 if args.min_samples is None else args.min_samples,
+                                     short_rows=args.short_rows)
+            w_new = mr.edges.w.cpu().numpy().view(np.uint32) if g.weights is None else mr.edges.weights.cpu().numpy()
+            counts = {k: np.asarray(v) for k, v in mr.info.items() if k != "ms_total"}
+            np.savez(args.mutual_reachability, core=mr.core_values().cpu().numpy(), w=w_new, **counts)
+            if not args.quiet:
+                print(f"Mutual reachability: k = {mr.info['k']}, {mr.info['raised_edges']} of {g.m} edges raised, "
+                      f"{mr.info['short_rows']} short rows, {mr.info['isolated']} isolated vertices, "
+                      f"max degree {mr.info['max_degree']}")
+                print(f"Mutual reachability saved to: {args.mutual_reachability}")
+        if args.hdbscan:
+            mcs = 5 if args.min_cluster_size is None else args.min_cluster_size
+            h = hdbscan(de, min_cluster_size=mcs, min_samples=args.min_samples, method=args.cluster_method,
+                        allow_single_cluster=args.allow_single_cluster, short_rows=args.short_rows)
+            c = h.clusters
+            arrays = {k: getattr(c, k).cpu().numpy() for k in (
+                "label", "probability", "point_cluster", "point_lambda", "cluster_head", "cluster_parent", "cluster_size",
+                "cluster_birth", "cluster_stability", "cluster_selected")}
+            for k in ("point_cluster", "cluster_head", "cluster_parent", "cluster_size"):
+                arrays[k] = arrays[k].view(np.uint32)
+            counts = {k: np.asarray(v) for k, v in c.info.items() if k != "ms_total"}
+            np.savez(args.hdbscan, core=h.reach.core_values().cpu().numpy(), in_mst=h.mst.in_mst_host(), **arrays, **counts)
+            if not args.quiet:
+                print(f"HDBSCAN: {c.info['num_selected']} clusters selected of {c.info['num_clusters']} in the condensed "
+                      f"tree, {c.info['num_noise']} noise vertices ({h.reach.info['raised_edges']} of {g.m} edges raised)")
+                print(f"HDBSCAN saved to: {args.hdbscan}")
     if args.paths:
         import numpy as np
 

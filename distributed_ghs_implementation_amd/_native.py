@@ -75,6 +75,7 @@ EXPORTED_SYMBOLS = (
     "ghs_forest_dendro_workspace_bytes", "ghs_forest_dendro_device", "ghs_forest_dendro_host",
     "ghs_forest_cluster_workspace_bytes", "ghs_forest_cluster_capacity", "ghs_forest_cluster_device",
     "ghs_forest_cluster_host",
+    "ghs_mutual_reach_workspace_bytes", "ghs_mutual_reach_device", "ghs_mutual_reach_host", "ghs_mutual_reach_phases",
 )
 
 
@@ -274,6 +275,46 @@ def cluster_args(min_cluster_size, method, allow_single_cluster):
     if method not in ("eom", "leaf"):
         raise ValueError(f"method: 'eom' or 'leaf' expected, got {method!r}")
     return mcs, (GHS_CLUSTER_LEAF if method == "leaf" else 0) | (GHS_CLUSTER_ALLOW_SINGLE if allow_single_cluster else 0)
+
+
+# the row classes of ghs_mutual_reach_device (include/ghs_mst.h GHS_MREACH_*): degrees from which one
+# workgroup, and from which the whole grid, selects a row
+GHS_MREACH_LANE_ROW_MAX = 32
+GHS_MREACH_BLOCK_ROW_MIN = 256
+GHS_MREACH_GRID_ROW_MIN = 32768
+
+
+class MreachResult(ctypes.Structure):
+    """ghs_mreach_result_t: what ghs_mutual_reach_device / ghs_mutual_reach_host found."""
+    _fields_ = [
+        ("short_rows", ctypes.c_uint64),
+        ("isolated", ctypes.c_uint64),
+        ("raised_edges", ctypes.c_uint64),
+        ("max_degree", ctypes.c_uint32),
+        ("block_rows", ctypes.c_uint32),
+        ("grid_rows", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+        ("ms_total", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+def mreach_args(min_samples, short_rows, include_self=False):
+    """k of the mutual-reachability entry points (0: include_self left nothing to select); ValueError
+    for what they would refuse."""
+    try:
+        k = int(min_samples)
+    except (TypeError, ValueError):
+        raise ValueError(f"min_samples must be an integer >= 1, got {min_samples!r}") from None
+    if k < 1 or k != min_samples:
+        raise ValueError(f"min_samples must be an integer >= 1, got {min_samples!r}")
+    if k >= (1 << 32):
+        raise ValueError(f"min_samples must be < 2^32, got {min_samples!r}")
+    if short_rows not in ("error", "clamp"):
+        raise ValueError(f"short_rows: 'error' or 'clamp' expected, got {short_rows!r}")
+    return k - 1 if include_self else k
 
 
 class PathsResult(ctypes.Structure):
@@ -619,6 +660,11 @@ def load():
             "ghs_forest_cluster_device": (i32, [u32, u64] + [vp] * 6 + [u32, u32] + [vp] * 10 + [vp, sz, vp,
                                                 P(ClusterResult)]),
             "ghs_forest_cluster_host": (i32, [u32, u64] + [vp] * 6 + [u32, u32] + [vp] * 10 + [P(ClusterResult)]),
+            # ABI 10 addition: core distances and mutual-reachability weights of a canonical edge list
+            "ghs_mutual_reach_workspace_bytes": (sz, [u32, u64]),
+            "ghs_mutual_reach_device": (i32, [u32, u64, vp, vp, vp, u32, vp, vp, vp, sz, vp, P(MreachResult)]),
+            "ghs_mutual_reach_host": (i32, [u32, u64, vp, vp, vp, u32, vp, vp, P(MreachResult)]),
+            "ghs_mutual_reach_phases": (i32, [i32, P(ctypes.c_double)]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(L, name)

@@ -105,6 +105,17 @@ class DeviceEdges:
         eids = flags_to_eids(in_mst, 0, self.m)
         return self.src[eids].to(torch.int64) & 0xFFFFFFFF
 
+    def mutual_reachability(self, min_samples=5, short_rows="error", include_self=False, in_place=False):
+        """`mutual_reachability` of this list: the core distances and the weights HDBSCAN wants."""
+        return mutual_reachability(self, min_samples=min_samples, short_rows=short_rows, include_self=include_self,
+                                   in_place=in_place)
+
+    def hdbscan(self, min_cluster_size=5, min_samples=None, method="eom", allow_single_cluster=False, short_rows="error",
+                include_self=False):
+        """`hdbscan` of this list: mutual reachability, the solve, the dendrogram and the clusters."""
+        return hdbscan(self, min_cluster_size=min_cluster_size, min_samples=min_samples, method=method,
+                       allow_single_cluster=allow_single_cluster, short_rows=short_rows, include_self=include_self)
+
     def u_host(self):
         """u as a host uint32 array (expanded from the offsets for a CSR-only list)."""
         import numpy as np
@@ -884,6 +895,149 @@ def forest_clusters(dendrogram, edges=None, heights=None, min_cluster_size=5, me
     K = int(res.num_clusters)
     return Clusters(n, label, prob, pc, pl, c_head[:K], c_par[:K], c_size[:K], c_birth[:K], c_stab[:K], c_sel[:K],
                     info=res.as_dict())
+
+
+class MutualReachability:
+    """What `mutual_reachability` found. edges: the re-weighted DeviceEdges (the input's u, v, off and
+    src, the new w; the input itself after in_place=True). core: per vertex the core distance as the
+    engine's uint32 weight (an int32 GPU tensor of uint32 bits; a rank for a rank-mapped list). info: the
+    fields of ghs_mreach_result_t as a dict, plus k (what the library was asked for)."""
+
+    def __init__(self, edges, core, info=None, rank_values=None):
+        self.edges, self.core, self.info = edges, core, info
+        self._rank_values = rank_values  # rank-mapped lists: the caller's value of every rank, as its bits
+
+    def core_values(self):
+        """The core distances in the caller's own units: for a rank-mapped list the caller's values of
+        the core ranks (of `edges.weights`' dtype; 0 for an isolated vertex), otherwise the uint32
+        weights as int64."""
+        idx = self.core.to(torch.int64) & 0xFFFFFFFF
+        e = self.edges
+        if e.weights is None:
+            return idx
+        if self._rank_values is None or e.m == 0:
+            return torch.zeros(e.n, dtype=e.weights.dtype, device=self.core.device)
+        vals = self._rank_values[idx].view(e.weights.dtype)
+        if self.info is None or self.info.get("isolated", 1):
+            touched = torch.zeros(e.n, dtype=torch.bool, device=self.core.device)
+            touched[e.u.to(torch.int64) & 0xFFFFFFFF] = True
+            touched[e.v.to(torch.int64) & 0xFFFFFFFF] = True
+            vals = torch.where(touched, vals, torch.zeros_like(vals))
+        return vals
+
+
+_BITS_OF = {1: torch.int8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
+
+
+def _rank_value_table(ranks, weights):
+    """The caller's value of every rank, as an integer tensor of the values' bits: table[r] = the bits
+    of weights[e] for any e with ranks[e] == r. Values that share a rank without sharing their bits
+    (-0.0 and +0.0) resolve to the larger bit pattern, the same on every run."""
+    bits = weights.view(_BITS_OF[weights.element_size()])
+    idx = ranks.to(torch.int64) & 0xFFFFFFFF
+    size = int(idx.max()) + 1
+    table = torch.zeros(size, dtype=bits.dtype, device=bits.device)
+    return table.scatter_reduce_(0, idx, bits, "amax", include_self=False)
+
+
+def mutual_reachability(edges, min_samples=5, short_rows="error", include_self=False, in_place=False):
+    """Core distances and mutual-reachability weights of a canonical edge list on the device
+    (ghs_mutual_reach_device, csrc/mreach.hip): the weights HDBSCAN wants. core[x] is the min_samples-th
+    smallest weight among the edges at x (repeated weights count separately), and every edge gets
+    max(core[u], core[v], w). Exact, the same bytes on every run, and only w changes: the result is
+    canonical with the same edge ids, offsets and `src`, so the solver and every forest module take it
+    as it is.
+    edges: a DeviceEdges with `u` present (a CSR-only list raises ValueError). min_samples >= 1, any
+    size. short_rows: what to do with a vertex that has edges but fewer than min_samples of them:
+    "error" raises ValueError naming their number; "clamp" takes the largest weight at that vertex (k
+    clamped to the degree). An isolated vertex has core 0 and is no error: it ends up as noise. The
+    policy "infinite core distance, drop the vertex's edges" would change the edge ids and is not
+    offered. include_self=True: the dense scikit-learn convention, where a point is its own first
+    neighbour: k = min_samples - 1, and for min_samples == 1 the weights come back unchanged with every
+    core 0, without a library call. in_place=True overwrites the input's w (and weights) instead of
+    allocating new ones.
+    For a rank-mapped list (`edges.weights` set) the new `weights` are the caller's values of the new
+    ranks, looked up in a rank -> value table scattered from (w, weights) in torch, and
+    `MutualReachability.core_values()` gives the core distances in the caller's units.
+    Returns a `MutualReachability` (edges, core, info). Runs on torch's current stream; a non-canonical
+    list raises GHSError (GHS_E_NONCANON)."""
+    k = _native.mreach_args(min_samples, short_rows, include_self)
+    if edges.u is None:
+        raise ValueError("mutual_reachability needs the COO form (u present); a CSR-only list is not supported")
+    n, m = edges.n, edges.m
+    L = _native.load()
+    _native.require_gpu()
+    dev = edges.device
+    ranked = edges.weights is not None and m > 0
+    with torch.cuda.device(dev):
+        core = torch.empty(n, dtype=torch.int32, device=dev)
+        res = _native.MreachResult()
+        if k == 0:
+            core.zero_()
+            w_out = edges.w if in_place else edges.w.clone()
+        else:
+            w_in = edges.w if edges.w.stride(0) == 1 or m == 0 else edges.w.contiguous()
+            w_out = w_in if in_place and w_in is edges.w else torch.empty(m, dtype=torch.int32, device=dev)
+            table = _rank_value_table(w_in, edges.weights) if ranked else None
+            ws_bytes = int(L.ghs_mutual_reach_workspace_bytes(n, m))
+            ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=dev)
+            _native.check(L.ghs_mutual_reach_device(n, m, _ptr(edges.u), _ptr(edges.v), _ptr(w_in), k, _ptr(core),
+                                                    _ptr(w_out), _ptr(ws), ws_bytes, _stream(), ctypes.byref(res)))
+            del ws
+    info = res.as_dict()
+    info["k"] = k
+    if k == 0:
+        out = edges if in_place else DeviceEdges(n, edges.u, edges.v, w_out, edges.off, edges.src,
+                                                 None if edges.weights is None else edges.weights.clone())
+        return MutualReachability(out, core, info)
+    if info["short_rows"] and short_rows == "error":
+        raise ValueError(f"{info['short_rows']} vertices have edges but fewer than min_samples = {min_samples}"
+                         f"{' (the point itself included)' if include_self else ''} of them; give every vertex at "
+                         "least that many neighbours, or pass short_rows='clamp' to use each one's largest weight")
+    weights = edges.weights
+    if ranked:
+        weights = table[w_out.to(torch.int64) & 0xFFFFFFFF].view(edges.weights.dtype)
+    if in_place:
+        if w_out is not edges.w:
+            edges.w.copy_(w_out)
+        if ranked:
+            edges.weights.copy_(weights)
+        out = edges
+    else:
+        out = DeviceEdges(n, edges.u, edges.v, w_out, edges.off, edges.src, weights)
+    return MutualReachability(out, core, info, rank_values=table if ranked else None)
+
+
+class HDBSCANResult:
+    """What `hdbscan` ran: reach (the MutualReachability), mst (the DeviceMST after run(), over
+    reach.edges), dendrogram, clusters (a Clusters) and labels (clusters.label: int32, -1 noise)."""
+
+    def __init__(self, reach, mst, dendrogram, clusters):
+        self.reach, self.mst, self.dendrogram, self.clusters = reach, mst, dendrogram, clusters
+
+    @property
+    def labels(self):
+        return self.clusters.label
+
+
+def hdbscan(edges, min_cluster_size=5, min_samples=None, method="eom", allow_single_cluster=False, short_rows="error",
+            include_self=False):
+    """HDBSCAN of a canonical edge list (a k-NN graph, a sparse distance matrix) end to end on the
+    device: `mutual_reachability` -> `DeviceMST(...).run()` -> `dendrogram()` -> `clusters()`.
+    min_samples=None means min_cluster_size; short_rows and include_self as `mutual_reachability` takes
+    them, method and allow_single_cluster as `forest_clusters` does. The input list is left as it is.
+    Returns an `HDBSCANResult` (reach, mst, dendrogram, clusters, labels). The binary merge order inside
+    a level of equal mutual-reachability weights is the engine's own ((w, eid)), as it is every
+    implementation's own: labels may differ from another HDBSCAN's where ties decide."""
+    _native.cluster_args(min_cluster_size, method, allow_single_cluster)
+    reach = mutual_reachability(edges, min_samples=min_cluster_size if min_samples is None else min_samples,
+                                short_rows=short_rows, include_self=include_self)
+    mst = DeviceMST(reach.edges)
+    mst.run()
+    dg = mst.dendrogram()
+    cl = dg.clusters(reach.edges, min_cluster_size=min_cluster_size, method=method,
+                     allow_single_cluster=allow_single_cluster)
+    return HDBSCANResult(reach, mst, dg, cl)
 
 
 class PathAnswers:

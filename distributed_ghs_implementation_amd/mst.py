@@ -436,6 +436,40 @@ def minimum_spanning_forest_edges(num_nodes, u, v, w, rank_weights=False):
     return out
 
 
+def hdbscan_edges(num_nodes, u, v, w, rank_weights=False, min_cluster_size=5, min_samples=None, method="eom",
+                  allow_single_cluster=False, short_rows="error", include_self=False, return_info=False):
+    """Raw edge arrays (a k-NN graph, a sparse distance matrix; as `minimum_spanning_forest_edges` takes
+    them) -> HDBSCAN end to end on the device: DeviceEdges.from_raw, then `device.hdbscan` (core
+    distances and mutual-reachability weights, the solve on them, the dendrogram, the cluster
+    extraction). Returns a dict of numpy arrays shaped like `MSTResult.clusters()` (label, probability,
+    point_cluster, point_lambda, cluster_head, cluster_parent, cluster_size, cluster_birth,
+    cluster_stability, cluster_selected) plus core (per vertex the core distance in the caller's units:
+    the caller's dtype with rank_weights=True, else int64) and mst_raw_ids (for every edge of the
+    mutual-reachability forest, the index of the caller's edge it is). min_samples=None means
+    min_cluster_size; short_rows ("error" / "clamp") and include_self as `device.mutual_reachability`
+    takes them. return_info=True: (dict, {"reach": ..., "cluster": ...})."""
+    from .device import DeviceEdges, hdbscan
+    n = int(num_nodes)
+    if n < 0 or n >= (1 << 32):
+        raise ValueError("num_nodes must be in [0, 2^32)")
+    # ValueError (bad values) before anything touches the device
+    _native.cluster_args(min_cluster_size, method, allow_single_cluster)
+    _native.mreach_args(min_cluster_size if min_samples is None else min_samples, short_rows, include_self)
+    edges = DeviceEdges.from_raw(n, u, v, w, rank_weights=rank_weights)
+    h = hdbscan(edges, min_cluster_size=min_cluster_size, min_samples=min_samples, method=method,
+                allow_single_cluster=allow_single_cluster, short_rows=short_rows, include_self=include_self)
+    c = h.clusters
+    out = {"label": c.label.cpu().numpy(), "probability": c.probability.cpu().numpy(),
+           "point_cluster": c.point_cluster.cpu().numpy().view(np.uint32), "point_lambda": c.point_lambda.cpu().numpy(),
+           "cluster_head": c.cluster_head.cpu().numpy().view(np.uint32),
+           "cluster_parent": c.cluster_parent.cpu().numpy().view(np.uint32),
+           "cluster_size": c.cluster_size.cpu().numpy().view(np.uint32), "cluster_birth": c.cluster_birth.cpu().numpy(),
+           "cluster_stability": c.cluster_stability.cpu().numpy(), "cluster_selected": c.cluster_selected.cpu().numpy(),
+           "core": h.reach.core_values().cpu().numpy(),
+           "mst_raw_ids": h.reach.edges.raw_eids(h.mst.in_mst).cpu().numpy().astype(np.int64)}
+    return (out, {"reach": h.reach.info, "cluster": c.info}) if return_info else out
+
+
 def fits_batch(graph):
     """True when the batch kernel takes the graph (GHS_BATCH_MAX_VERTICES / GHS_BATCH_MAX_EDGES)."""
     return graph.n <= _native.BATCH_MAX_VERTICES and graph.m <= _native.BATCH_MAX_EDGES

@@ -957,6 +957,63 @@ int ghs_forest_cluster_host(uint32_t n, uint64_t t, const uint32_t *leaf_parent,
                             uint32_t *cluster_size, double *cluster_birth, double *cluster_stability,
                             uint8_t *cluster_selected, ghs_cluster_result_t *result);
 
+/* ---- core distances and mutual reachability: which weights does HDBSCAN want? (ABI 10 addition) -----
+ * HDBSCAN clusters the minimum spanning forest of the mutual-reachability weights, not of the weights
+ * it is given: w_out[e] = max(core[u[e]], core[v[e]], w[e]), core[x] = the distance from x to its k-th
+ * nearest neighbour (k = min_samples). On a canonical edge list (a k-NN graph, a sparse distance
+ * matrix):
+ *   deg(x)   the canonical edges with x at either end;
+ *   core[x]  deg(x) >= k: the k-th smallest weight among the edges at x (k counts from 1, repeated
+ *            weights count separately); 0 < deg(x) < k (a short row): the largest weight at x (k clamped
+ *            to the degree); deg(x) == 0 (isolated): 0.
+ * Any k >= 1. A k-th smallest element and a max are order statistics: exact on uint32, the same bytes on
+ * every run, and they commute with the monotone rank map of rank-mapped weights. Only w changes, so the
+ * re-weighted list is canonical with the same edge ids. d_w_out may be exactly d_w (in place) or NULL
+ * (core distances only).
+ * Method (csrc/mreach.hip). Rows: the forward row of x is the run of x in the sorted u (offsets by one
+ * lower bound per vertex); the reverse row is the run of x in w sorted by v (stable rocPRIM pairs sort
+ * over the bits of n, one lower bound per vertex). Select, by degree: below
+ * GHS_MREACH_BLOCK_ROW_MIN the row stays in registers (4 values per lane; 8 lanes per row up to
+ * GHS_MREACH_LANE_ROW_MAX, a wave above) and the k-th value is built bit by bit from the top with
+ * ballots and popcounts; from GHS_MREACH_BLOCK_ROW_MIN one workgroup per row runs a four-pass 8-bit
+ * radix select over an LDS histogram; from GHS_MREACH_GRID_ROW_MIN the rows are listed and every digit
+ * pass histograms all of them with the whole grid (integer atomics: any order gives the same counts).
+ * Re-weight: one streaming pass, four edges per lane. Host syncs: the canonicity check's and one more.
+ * Workspace (ghs_mutual_reach_workspace_bytes): 8 B per vertex + 8 B per edge + rocPRIM's sort storage
+ * + the row lists (4 B per GHS_MREACH_LANE_ROW_MAX + 1 edge ends and less) + 1 KiB + 12 B per possible
+ * grid row. m == 0: 0.
+ * Errors, checked before any device work (so GHS_E_ARG, not GHS_E_NODEVICE, on a host without GPU): a
+ * NULL result, k == 0, m >= 2^31, NULL or misaligned pointers (16 bytes for u / v / w / w_out /
+ * workspace, 4 for core), d_w_out overlapping d_w without being equal to it (or overlapping u, v or
+ * core), d_core overlapping u, v or w: GHS_E_ARG; workspace_bytes short: GHS_E_NOMEM. n == 0: GHS_OK,
+ * nothing written. m == 0, n > 0: every core is 0 and only d_core is needed. A non-canonical list
+ * (ghs_check_canonical): GHS_E_NONCANON before any index is formed from it. */
+#define GHS_MREACH_LANE_ROW_MAX 32u       /* up to here 8 lanes hold a row */
+#define GHS_MREACH_BLOCK_ROW_MIN 256u     /* from here one workgroup selects a row (below: one wave at most) */
+#define GHS_MREACH_GRID_ROW_MIN 32768u    /* from here every workgroup takes tiles of the row */
+typedef struct ghs_mreach_result {   /* 48 bytes */
+  uint64_t short_rows;      /* vertices with 0 < deg < k (k was clamped to the degree) */
+  uint64_t isolated;        /* vertices with deg == 0 (core 0) */
+  uint64_t raised_edges;    /* edges with w_out > w (0 when d_w_out is NULL) */
+  uint32_t max_degree;
+  uint32_t block_rows;      /* rows selected by one workgroup each */
+  uint32_t grid_rows;       /* rows selected by the whole grid */
+  uint32_t reserved;
+  double   ms_total;        /* host wall time of the call */
+} ghs_mreach_result_t;
+size_t ghs_mutual_reach_workspace_bytes(uint32_t n, uint64_t m);   /* host only, no GPU needed */
+int ghs_mutual_reach_device(uint32_t n, uint64_t m, const uint32_t *d_u, const uint32_t *d_v, const uint32_t *d_w,
+                            uint32_t k, uint32_t *d_core /* n */,
+                            uint32_t *d_w_out /* m; may be NULL; may be exactly d_w (in place) */,
+                            void *d_workspace, size_t workspace_bytes, void *stream, ghs_mreach_result_t *result);
+/* the same for host arrays (copy in, run, copy out on the default stream); the argument errors above
+ * except the alignments and the workspace, then GHS_E_NODEVICE without a GPU */
+int ghs_mutual_reach_host(uint32_t n, uint64_t m, const uint32_t *u, const uint32_t *v, const uint32_t *w, uint32_t k,
+                          uint32_t *core, uint32_t *w_out, ghs_mreach_result_t *result);
+/* opt-in HIP-event times of the calling thread's last ghs_mutual_reach_device: ms[3] = rows, select,
+ * re-weight (read before `enable` takes effect for the next call); diagnostic */
+int ghs_mutual_reach_phases(int enable, double *ms);
+
 /* device-side canonicity check: *ok = 1 iff u < v < n and (u, v) strictly ascending */
 int ghs_check_canonical(uint32_t n, uint64_t m, const uint32_t *d_u, const uint32_t *d_v, void *stream, int *ok);
 
