@@ -199,7 +199,10 @@ int ghs_flags_to_eids(const uint8_t *d_in_mst, uint64_t lo, uint64_t hi, uint32_
  * are streamed out of it (edge-centric: every edge is a candidate for both of its fragments). */
 void ghs_default_config(ghs_config_t *cfg);
 
-/* workspace bytes for ghs_mst_device / a solver handle owning local_edges canonical edges */
+/* workspace bytes for ghs_mst_device / a solver handle owning local_edges canonical edges. The solver
+ * carves 256-byte aligned arrays out of its workspace: d_workspace must be 256-byte aligned (GHS_E_ARG
+ * otherwise; ghs_mst_device, ghs_mst_device_csr, ghs_solver_create, ghs_solver_create_csr). Every other
+ * entry point takes a 16-byte aligned workspace. */
 size_t ghs_workspace_bytes(uint32_t n, uint64_t m, uint64_t local_edges);
 
 /* Whole MST on one device: canonical edges -> d_in_mst (m bytes, 1 = in the MSF) + totals.
