@@ -224,13 +224,6 @@ void launch_class(BatchArgs a, uint32_t B, hipStream_t st) {
   k_batch<(int)CLS_N[C], (int)CLS_T[C]><<<B < full ? B : full, CLS_T[C], 0, st>>>(a);
 }
 
-struct DevBuf {
-  void *p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-};
-
 }  // namespace
 
 extern "C" size_t ghs_batch_workspace_bytes(uint32_t num_graphs) {
@@ -279,37 +272,31 @@ extern "C" int ghs_mst_batch_host(uint32_t num_graphs, const uint32_t *nvert, co
   const size_t M = eoff[B];
   if (M >= (1ull << 31)) GHS_FAIL(GHS_E_ARG, "the batch's edge count must be < 2^31");
   if (M && (!u || !v || !w || !in_mst)) GHS_FAIL(GHS_E_ARG, "NULL host pointer");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) GHS_FAIL(GHS_E_NODEVICE, "no HIP device");
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  if (int e = ghs::require_device()) return e;
   const size_t ws = ghs_batch_workspace_bytes(B);
-  const size_t off_n = 0, off_e = off_n + al((size_t)B * 4), off_u = off_e + al(((size_t)B + 1) * 4),
-               off_v = off_u + al(M * 4), off_w = off_v + al(M * 4), off_f = off_w + al(M * 4),
-               off_r = off_f + al(M ? M : 1), off_ws = off_r + al((size_t)B * sizeof(ghs_batch_result_t)),
-               total = off_ws + al(ws);
-  DevBuf buf;
-  if (hipMalloc(&buf.p, total) != hipSuccess) {
+  ghs::Staging dev;
+  const auto d_n = dev.take<uint32_t>(B), d_e = dev.take<uint32_t>((size_t)B + 1);
+  const auto d_u = dev.take<uint32_t>(M), d_v = dev.take<uint32_t>(M), d_w = dev.take<uint32_t>(M);
+  const auto d_f = dev.take<uint8_t>(M);
+  const auto d_r = dev.take<ghs_batch_result_t>(B);
+  const auto d_ws = dev.take<char>(ws);
+  if (dev.alloc() != hipSuccess) {
     (void)hipGetLastError();
     GHS_FAIL(GHS_E_NOMEM, "hipMalloc of the batch buffers failed");
   }
-  char *b = (char *)buf.p;
   hipStream_t st = nullptr;
-  GHS_HIP_CHECK(hipMemcpyAsync(b + off_n, nvert, (size_t)B * 4, hipMemcpyHostToDevice, st));
-  GHS_HIP_CHECK(hipMemcpyAsync(b + off_e, eoff, ((size_t)B + 1) * 4, hipMemcpyHostToDevice, st));
-  if (M) {
-    GHS_HIP_CHECK(hipMemcpyAsync(b + off_u, u, M * 4, hipMemcpyHostToDevice, st));
-    GHS_HIP_CHECK(hipMemcpyAsync(b + off_v, v, M * 4, hipMemcpyHostToDevice, st));
-    GHS_HIP_CHECK(hipMemcpyAsync(b + off_w, w, M * 4, hipMemcpyHostToDevice, st));
-    // a slice behind non-monotone offsets is never written by the kernel: its flags read 0
-    GHS_HIP_CHECK(hipMemsetAsync(b + off_f, 0, M, st));
-  }
-  int rc = ghs_mst_batch_device(B, (uint32_t *)(b + off_n), (uint32_t *)(b + off_e), (uint32_t *)(b + off_u),
-                                (uint32_t *)(b + off_v), (uint32_t *)(b + off_w), b + off_ws, ws,
-                                (uint8_t *)(b + off_f), (ghs_batch_result_t *)(b + off_r), st);
+  GHS_HIP_CHECK(dev.up(d_n, nvert, st));
+  GHS_HIP_CHECK(dev.up(d_e, eoff, st));
+  GHS_HIP_CHECK(dev.up(d_u, u, st));
+  GHS_HIP_CHECK(dev.up(d_v, v, st));
+  GHS_HIP_CHECK(dev.up(d_w, w, st));
+  // a slice behind non-monotone offsets is never written by the kernel: its flags read 0
+  if (M) GHS_HIP_CHECK(hipMemsetAsync(dev.at(d_f), 0, M, st));
+  int rc = ghs_mst_batch_device(B, dev.at(d_n), dev.at(d_e), dev.at(d_u), dev.at(d_v), dev.at(d_w), dev.at(d_ws), ws,
+                                dev.at(d_f), dev.at(d_r), st);
   if (rc) return rc;
-  if (M) GHS_HIP_CHECK(hipMemcpyAsync(in_mst, b + off_f, M, hipMemcpyDeviceToHost, st));
-  GHS_HIP_CHECK(hipMemcpyAsync(results, b + off_r, (size_t)B * sizeof(ghs_batch_result_t), hipMemcpyDeviceToHost, st));
-  GHS_HIP_CHECK(hipStreamSynchronize(st));
+  GHS_HIP_CHECK(dev.down(in_mst, d_f, M));
+  GHS_HIP_CHECK(dev.down(results, d_r, B));
   for (uint32_t g = 0; g < B; ++g) {
     const uint32_t s = results[g].status;
     if (s == 1) GHS_FAIL(GHS_E_NONCANON, "batch graph " + std::to_string(g) + ": edge slice is not canonical");

@@ -989,59 +989,45 @@ int ghs_forest_cluster_host(uint32_t n, uint64_t t, const uint32_t *leaf_parent,
   if (!label || !point_cluster || (t && (!leaf_parent || !merge_parent || !child_a || !child_b || !size || !height)) ||
       (cap && (!cluster_head || !cluster_parent || !cluster_size || !cluster_birth || !cluster_stability || !cluster_selected)))
     GHS_FAIL(GHS_E_ARG, "NULL host pointer");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) GHS_FAIL(GHS_E_NODEVICE, "no HIP device");
+  if (int e = ghs::require_device()) return e;
   const size_t ws = ghs_forest_cluster_workspace_bytes(n, t, min_cluster_size);
-  const size_t T = (size_t)(t ? t : 1), C = (size_t)(cap ? cap : 1), N = n;
-  size_t o = 0;
-  auto take = [&o](size_t bytes) {
-    const size_t at = o;
-    o += align256(bytes);
-    return at;
-  };
-  const size_t i_leaf = take(N * 4), i_mp = take(T * 4), i_ca = take(T * 4), i_cb = take(T * 4), i_sz = take(T * 4),
-               i_h = take(T * 8);
-  const size_t o_lab = take(N * 4), o_pr = take(N * 8), o_pc = take(N * 4), o_pl = take(N * 8);
-  const size_t c_head = take(C * 4), c_par = take(C * 4), c_sz = take(C * 4), c_bi = take(C * 8), c_st = take(C * 8),
-               c_sel = take(C);
-  const size_t o_ws = take(ws ? ws : 1);
-  struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() {
-      if (p) (void)hipFree(p);
-    }
-  } buf;
-  GHS_HIP_CHECK(hipMalloc(&buf.p, o));
-  char *b = (char *)buf.p;
+  ghs::Staging s;
+  // t == 0: the six inputs may be NULL, and none is read
+  const size_t n_in = t ? n : 0;
+  const auto i_leaf = s.take<uint32_t>(n_in), i_mp = s.take<uint32_t>(t), i_ca = s.take<uint32_t>(t), i_cb = s.take<uint32_t>(t),
+             i_sz = s.take<uint32_t>(t);
+  const auto i_h = s.take<double>(t);
+  const auto o_lab = s.take<int32_t>(n);
+  const auto o_pc = s.take<uint32_t>(n);
+  const auto o_pr = s.take<double>(n), o_pl = s.take<double>(n);
+  const auto c_head = s.take<uint32_t>(cap), c_par = s.take<uint32_t>(cap), c_sz = s.take<uint32_t>(cap);
+  const auto c_bi = s.take<double>(cap), c_st = s.take<double>(cap);
+  const auto c_sel = s.take<uint8_t>(cap);
+  const auto d_ws = s.take<char>(ws);
+  GHS_HIP_CHECK(s.alloc());
   hipStream_t st = nullptr;
-  if (t) {
-    GHS_HIP_CHECK(hipMemcpyAsync(b + i_leaf, leaf_parent, N * 4, hipMemcpyHostToDevice, st));
-    GHS_HIP_CHECK(hipMemcpyAsync(b + i_mp, merge_parent, t * 4, hipMemcpyHostToDevice, st));
-    GHS_HIP_CHECK(hipMemcpyAsync(b + i_ca, child_a, t * 4, hipMemcpyHostToDevice, st));
-    GHS_HIP_CHECK(hipMemcpyAsync(b + i_cb, child_b, t * 4, hipMemcpyHostToDevice, st));
-    GHS_HIP_CHECK(hipMemcpyAsync(b + i_sz, size, t * 4, hipMemcpyHostToDevice, st));
-    GHS_HIP_CHECK(hipMemcpyAsync(b + i_h, height, t * 8, hipMemcpyHostToDevice, st));
-  }
-  const int rc = ghs_forest_cluster_device(
-      n, t, (uint32_t *)(b + i_leaf), (uint32_t *)(b + i_mp), (uint32_t *)(b + i_ca), (uint32_t *)(b + i_cb),
-      (uint32_t *)(b + i_sz), (double *)(b + i_h), min_cluster_size, flags, (int32_t *)(b + o_lab),
-      probability ? (double *)(b + o_pr) : nullptr, (uint32_t *)(b + o_pc), point_lambda ? (double *)(b + o_pl) : nullptr,
-      (uint32_t *)(b + c_head), (uint32_t *)(b + c_par), (uint32_t *)(b + c_sz), (double *)(b + c_bi), (double *)(b + c_st),
-      (uint8_t *)(b + c_sel), b + o_ws, ws, st, result);
+  GHS_HIP_CHECK(s.up(i_leaf, leaf_parent, st));
+  GHS_HIP_CHECK(s.up(i_mp, merge_parent, st));
+  GHS_HIP_CHECK(s.up(i_ca, child_a, st));
+  GHS_HIP_CHECK(s.up(i_cb, child_b, st));
+  GHS_HIP_CHECK(s.up(i_sz, size, st));
+  GHS_HIP_CHECK(s.up(i_h, height, st));
+  const int rc = ghs_forest_cluster_device(n, t, s.at(i_leaf), s.at(i_mp), s.at(i_ca), s.at(i_cb), s.at(i_sz), s.at(i_h),
+                                           min_cluster_size, flags, s.at(o_lab), s.at(o_pr, probability), s.at(o_pc),
+                                           s.at(o_pl, point_lambda), s.at(c_head), s.at(c_par), s.at(c_sz), s.at(c_bi),
+                                           s.at(c_st), s.at(c_sel), s.at(d_ws), ws, st, result);
   if (rc) return rc;
-  GHS_HIP_CHECK(hipMemcpy(label, b + o_lab, N * 4, hipMemcpyDeviceToHost));
-  GHS_HIP_CHECK(hipMemcpy(point_cluster, b + o_pc, N * 4, hipMemcpyDeviceToHost));
-  if (probability) GHS_HIP_CHECK(hipMemcpy(probability, b + o_pr, N * 8, hipMemcpyDeviceToHost));
-  if (point_lambda) GHS_HIP_CHECK(hipMemcpy(point_lambda, b + o_pl, N * 8, hipMemcpyDeviceToHost));
-  const size_t K = result->num_clusters;
-  if (K) {
-    GHS_HIP_CHECK(hipMemcpy(cluster_head, b + c_head, K * 4, hipMemcpyDeviceToHost));
-    GHS_HIP_CHECK(hipMemcpy(cluster_parent, b + c_par, K * 4, hipMemcpyDeviceToHost));
-    GHS_HIP_CHECK(hipMemcpy(cluster_size, b + c_sz, K * 4, hipMemcpyDeviceToHost));
-    GHS_HIP_CHECK(hipMemcpy(cluster_birth, b + c_bi, K * 8, hipMemcpyDeviceToHost));
-    GHS_HIP_CHECK(hipMemcpy(cluster_stability, b + c_st, K * 8, hipMemcpyDeviceToHost));
-    GHS_HIP_CHECK(hipMemcpy(cluster_selected, b + c_sel, K, hipMemcpyDeviceToHost));
-  }
+  GHS_HIP_CHECK(s.down(label, o_lab, n));
+  GHS_HIP_CHECK(s.down(point_cluster, o_pc, n));
+  GHS_HIP_CHECK(s.down(probability, o_pr, n));
+  GHS_HIP_CHECK(s.down(point_lambda, o_pl, n));
+  const size_t K = result->num_clusters;  // only the clusters that exist
+  GHS_HIP_CHECK(s.down(cluster_head, c_head, K));
+  GHS_HIP_CHECK(s.down(cluster_parent, c_par, K));
+  GHS_HIP_CHECK(s.down(cluster_size, c_sz, K));
+  GHS_HIP_CHECK(s.down(cluster_birth, c_bi, K));
+  GHS_HIP_CHECK(s.down(cluster_stability, c_st, K));
+  GHS_HIP_CHECK(s.down(cluster_selected, c_sel, K));
   return GHS_OK;
 }
 

@@ -101,3 +101,62 @@ void ghs_release_eid_temps();
     ::ghs::set_error(msg);           \
     return (code);                   \
   } while (0)
+
+// ---- the host-buffer forms' staging (host only) -------------------------------------------------
+namespace ghs {
+
+// what every host-buffer form asks once its arguments are checked
+inline int require_device() {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) GHS_FAIL(GHS_E_NODEVICE, "no HIP device");
+  return GHS_OK;
+}
+
+// The device side of a host-buffer form: one hipMalloc, cut into 256-byte aligned typed pieces and
+// freed on scope exit. take() every piece, alloc(), then at() / up() / down().
+class Staging {
+ public:
+  template <typename T>
+  struct Piece {
+    size_t off, count;
+  };
+  Staging() = default;
+  Staging(const Staging &) = delete;
+  Staging &operator=(const Staging &) = delete;
+  ~Staging() {
+    if (base_) (void)hipFree(base_);
+  }
+  // a piece of `count` elements (an empty one still takes an aligned step: its address is its own)
+  template <typename T>
+  Piece<T> take(size_t count) {
+    const Piece<T> p{total_, count};
+    total_ += ((count ? count * sizeof(T) : 1) + 255) & ~(size_t)255;
+    return p;
+  }
+  hipError_t alloc() { return hipMalloc((void **)&base_, total_); }
+  template <typename T>
+  T *at(Piece<T> p) const {
+    return (T *)(base_ + p.off);
+  }
+  // nullptr for an optional output the caller did not ask for
+  template <typename T>
+  T *at(Piece<T> p, const void *host) const {
+    return host ? at(p) : nullptr;
+  }
+  // the whole piece from the host, asynchronously
+  template <typename T>
+  hipError_t up(Piece<T> p, const T *host, hipStream_t st) const {
+    return p.count ? hipMemcpyAsync(at(p), host, p.count * sizeof(T), hipMemcpyHostToDevice, st) : hipSuccess;
+  }
+  // exactly `count` elements to the host, synchronously; nothing for a NULL host pointer
+  template <typename T>
+  hipError_t down(T *host, Piece<T> p, size_t count) const {
+    return host && count ? hipMemcpy(host, at(p), count * sizeof(T), hipMemcpyDeviceToHost) : hipSuccess;
+  }
+
+ private:
+  char *base_ = nullptr;
+  size_t total_ = 0;
+};
+
+}  // namespace ghs

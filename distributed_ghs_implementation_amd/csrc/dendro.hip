@@ -886,41 +886,31 @@ int ghs_forest_dendro_host(uint32_t n, uint64_t m, const uint32_t *u, const uint
   if (m >= (1ull << 31)) GHS_FAIL(GHS_E_ARG, "m must be < 2^31");
   if (!leaf_parent || (m && (!u || !v || !w || !in_mst || !merge_eid || !merge_parent)))
     GHS_FAIL(GHS_E_ARG, "NULL host pointer");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) GHS_FAIL(GHS_E_NODEVICE, "no HIP device");
+  if (int e = ghs::require_device()) return e;
   const size_t ws = m ? ghs_forest_dendro_workspace_bytes(n, m) : 0;
   const uint64_t C = m < (uint64_t)n - 1 ? m : (uint64_t)n - 1;
-  const size_t cb = align256((size_t)(C ? C : 1) * 4), mb = align256((size_t)(m ? m : 1) * 4);
-  const size_t off_u = 0, off_v = off_u + mb, off_w = off_v + mb, off_f = off_w + mb, off_l = off_f + align256(m ? m : 1),
-               off_o = off_l + align256((size_t)n * 4), off_ws = off_o + 5 * cb, total = off_ws + align256(ws ? ws : 1);
-  struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() {
-      if (p) (void)hipFree(p);
-    }
-  } buf;
-  GHS_HIP_CHECK(hipMalloc(&buf.p, total));
-  char *b = (char *)buf.p;
-  hipStream_t st = nullptr;
-  if (m) {
-    GHS_HIP_CHECK(hipMemcpyAsync(b + off_u, u, m * 4, hipMemcpyHostToDevice, st));
-    GHS_HIP_CHECK(hipMemcpyAsync(b + off_v, v, m * 4, hipMemcpyHostToDevice, st));
-    GHS_HIP_CHECK(hipMemcpyAsync(b + off_w, w, m * 4, hipMemcpyHostToDevice, st));
-    GHS_HIP_CHECK(hipMemcpyAsync(b + off_f, in_mst, m, hipMemcpyHostToDevice, st));
-  }
-  uint32_t *d_out[5];
-  for (int k = 0; k < 5; ++k) d_out[k] = (uint32_t *)(b + off_o + k * cb);
+  ghs::Staging s;
+  const auto d_u = s.take<uint32_t>(m), d_v = s.take<uint32_t>(m), d_w = s.take<uint32_t>(m);
+  const auto d_f = s.take<uint8_t>(m);
+  const auto d_l = s.take<uint32_t>(n);
   uint32_t *h_out[5] = {merge_eid, merge_parent, child_a, child_b, size};
-  int rc = ghs_forest_dendro_device(n, m, (uint32_t *)(b + off_u), (uint32_t *)(b + off_v), (uint32_t *)(b + off_w),
-                                    (uint8_t *)(b + off_f), (uint32_t *)(b + off_l), d_out[0], d_out[1],
-                                    child_a ? d_out[2] : nullptr, child_b ? d_out[3] : nullptr, size ? d_out[4] : nullptr,
-                                    b + off_ws, ws, st, result);
+  ghs::Staging::Piece<uint32_t> d_out[5];
+  for (auto &p : d_out) p = s.take<uint32_t>(C);
+  const auto d_ws = s.take<char>(ws);
+  GHS_HIP_CHECK(s.alloc());
+  hipStream_t st = nullptr;
+  GHS_HIP_CHECK(s.up(d_u, u, st));
+  GHS_HIP_CHECK(s.up(d_v, v, st));
+  GHS_HIP_CHECK(s.up(d_w, w, st));
+  GHS_HIP_CHECK(s.up(d_f, in_mst, st));
+  int rc = ghs_forest_dendro_device(n, m, s.at(d_u), s.at(d_v), s.at(d_w), s.at(d_f), s.at(d_l), s.at(d_out[0]), s.at(d_out[1]),
+                                    s.at(d_out[2], child_a), s.at(d_out[3], child_b), s.at(d_out[4], size), s.at(d_ws), ws, st,
+                                    result);
   if (rc) return rc;
-  GHS_HIP_CHECK(hipMemcpy(leaf_parent, b + off_l, (size_t)n * 4, hipMemcpyDeviceToHost));
-  const size_t t = (size_t)result->flagged_edges;
-  if (t && result->is_forest)
-    for (int k = 0; k < 5; ++k)
-      if (h_out[k]) GHS_HIP_CHECK(hipMemcpy(h_out[k], d_out[k], t * 4, hipMemcpyDeviceToHost));
+  GHS_HIP_CHECK(s.down(leaf_parent, d_l, n));
+  // only the t merges that exist, and none of them when the flags close a cycle
+  const size_t t = result->is_forest ? (size_t)result->flagged_edges : 0;
+  for (int k = 0; k < 5; ++k) GHS_HIP_CHECK(s.down(h_out[k], d_out[k], t));
   return GHS_OK;
 }
 

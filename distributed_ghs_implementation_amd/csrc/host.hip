@@ -7,40 +7,28 @@
 
 #include "common.h"
 
-namespace {
-struct DevBuf {
-  void *p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-};
-}  // namespace
+using ghs::Staging;
 
 extern "C" int ghs_mst_host(uint32_t n, uint64_t m, const uint32_t *u, const uint32_t *v, const uint32_t *w,
                             uint8_t *in_mst, ghs_result_t *result, ghs_round_stats_t *stats) {
   if (m && (!u || !v || !w || !in_mst)) GHS_FAIL(GHS_E_ARG, "NULL host pointer");
   if (m >= (1ull << 31)) GHS_FAIL(GHS_E_ARG, "m must be < 2^31");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) GHS_FAIL(GHS_E_NODEVICE, "no HIP device");
+  if (int e = ghs::require_device()) return e;
   // canonicity is validated on the device by the solve's first pass (k_select, GHS_E_NONCANON
   // before any id indexes an array): no serial host loop in front of the copy
   const size_t ws = ghs_workspace_bytes(n, m, m);
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t off_u = 0, off_v = off_u + al(m * 4), off_w = off_v + al(m * 4), off_mst = off_w + al(m * 4),
-               off_ws = off_mst + al(m ? m : 1), total = off_ws + al(ws);
-  DevBuf buf;
-  GHS_HIP_CHECK(hipMalloc(&buf.p, total));
-  char *b = (char *)buf.p;
+  Staging s;
+  const auto d_u = s.take<uint32_t>(m), d_v = s.take<uint32_t>(m), d_w = s.take<uint32_t>(m);
+  const auto d_mst = s.take<uint8_t>(m);
+  const auto d_ws = s.take<char>(ws);
+  GHS_HIP_CHECK(s.alloc());
   hipStream_t st = nullptr;
-  if (m) {
-    GHS_HIP_CHECK(hipMemcpyAsync(b + off_u, u, m * 4, hipMemcpyHostToDevice, st));
-    GHS_HIP_CHECK(hipMemcpyAsync(b + off_v, v, m * 4, hipMemcpyHostToDevice, st));
-    GHS_HIP_CHECK(hipMemcpyAsync(b + off_w, w, m * 4, hipMemcpyHostToDevice, st));
-  }
-  int rc = ghs_mst_device(n, m, (uint32_t *)(b + off_u), (uint32_t *)(b + off_v), (uint32_t *)(b + off_w), nullptr,
-                          b + off_ws, ws, (uint8_t *)(b + off_mst), st, result, stats);
+  GHS_HIP_CHECK(s.up(d_u, u, st));
+  GHS_HIP_CHECK(s.up(d_v, v, st));
+  GHS_HIP_CHECK(s.up(d_w, w, st));
+  int rc = ghs_mst_device(n, m, s.at(d_u), s.at(d_v), s.at(d_w), nullptr, s.at(d_ws), ws, s.at(d_mst), st, result, stats);
   if (rc) return rc;
-  if (m) GHS_HIP_CHECK(hipMemcpy(in_mst, b + off_mst, m, hipMemcpyDeviceToHost));
+  GHS_HIP_CHECK(s.down(in_mst, d_mst, m));
   return GHS_OK;
 }
 
@@ -61,27 +49,23 @@ extern "C" int ghs_forest_labels_host(uint32_t n, uint64_t m, const uint32_t *u,
   }
   if (m >= (1ull << 31)) GHS_FAIL(GHS_E_ARG, "m must be < 2^31");
   if (!labels || (m && (!u || !v || !w || !in_mst))) GHS_FAIL(GHS_E_ARG, "NULL host pointer");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) GHS_FAIL(GHS_E_NODEVICE, "no HIP device");
+  if (int e = ghs::require_device()) return e;
   const size_t ws = m ? ghs_forest_labels_workspace_bytes(n, m) : 0;
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t off_u = 0, off_v = off_u + al(m * 4), off_w = off_v + al(m * 4), off_f = off_w + al(m * 4),
-               off_l = off_f + al(m ? m : 1), off_ws = off_l + al((size_t)n * 4), total = off_ws + al(ws ? ws : 1);
-  DevBuf buf;
-  GHS_HIP_CHECK(hipMalloc(&buf.p, total));
-  char *b = (char *)buf.p;
+  Staging s;
+  const auto d_u = s.take<uint32_t>(m), d_v = s.take<uint32_t>(m), d_w = s.take<uint32_t>(m);
+  const auto d_f = s.take<uint8_t>(m);
+  const auto d_l = s.take<uint32_t>(n);
+  const auto d_ws = s.take<char>(ws);
+  GHS_HIP_CHECK(s.alloc());
   hipStream_t st = nullptr;
-  if (m) {
-    GHS_HIP_CHECK(hipMemcpyAsync(b + off_u, u, m * 4, hipMemcpyHostToDevice, st));
-    GHS_HIP_CHECK(hipMemcpyAsync(b + off_v, v, m * 4, hipMemcpyHostToDevice, st));
-    GHS_HIP_CHECK(hipMemcpyAsync(b + off_w, w, m * 4, hipMemcpyHostToDevice, st));
-    GHS_HIP_CHECK(hipMemcpyAsync(b + off_f, in_mst, m, hipMemcpyHostToDevice, st));
-  }
-  int rc = ghs_forest_labels_device(n, m, (uint32_t *)(b + off_u), (uint32_t *)(b + off_v), (uint32_t *)(b + off_w),
-                                    (uint8_t *)(b + off_f), mode, param, (uint32_t *)(b + off_l), b + off_ws, ws, st,
-                                    result);
+  GHS_HIP_CHECK(s.up(d_u, u, st));
+  GHS_HIP_CHECK(s.up(d_v, v, st));
+  GHS_HIP_CHECK(s.up(d_w, w, st));
+  GHS_HIP_CHECK(s.up(d_f, in_mst, st));
+  int rc = ghs_forest_labels_device(n, m, s.at(d_u), s.at(d_v), s.at(d_w), s.at(d_f), mode, param, s.at(d_l), s.at(d_ws), ws,
+                                    st, result);
   if (rc) return rc;
-  GHS_HIP_CHECK(hipMemcpy(labels, b + off_l, (size_t)n * 4, hipMemcpyDeviceToHost));
+  GHS_HIP_CHECK(s.down(labels, d_l, n));
   return GHS_OK;
 }
 
@@ -98,33 +82,70 @@ extern "C" int ghs_forest_root_host(uint32_t n, uint64_t m, const uint32_t *u, c
   }
   if (m >= (1ull << 31)) GHS_FAIL(GHS_E_ARG, "m must be < 2^31");
   if (!parent || !parent_eid || !depth || (m && (!u || !v || !in_mst))) GHS_FAIL(GHS_E_ARG, "NULL host pointer");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) GHS_FAIL(GHS_E_NODEVICE, "no HIP device");
+  if (int e = ghs::require_device()) return e;
   const size_t ws = m ? ghs_forest_root_workspace_bytes(n, m) : 0;
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t nb = al((size_t)n * 4);
-  const size_t off_u = 0, off_v = off_u + al(m * 4), off_f = off_v + al(m * 4), off_o = off_f + al(m ? m : 1),
-               off_ws = off_o + 5 * nb, total = off_ws + al(ws ? ws : 1);
-  DevBuf buf;
-  GHS_HIP_CHECK(hipMalloc(&buf.p, total));
-  char *b = (char *)buf.p;
-  hipStream_t st = nullptr;
-  if (m) {
-    GHS_HIP_CHECK(hipMemcpyAsync(b + off_u, u, m * 4, hipMemcpyHostToDevice, st));
-    GHS_HIP_CHECK(hipMemcpyAsync(b + off_v, v, m * 4, hipMemcpyHostToDevice, st));
-    GHS_HIP_CHECK(hipMemcpyAsync(b + off_f, in_mst, m, hipMemcpyHostToDevice, st));
-  }
-  uint32_t *d_out[5];
-  for (int k = 0; k < 5; ++k) d_out[k] = (uint32_t *)(b + off_o + k * nb);
-  int rc = ghs_forest_root_device(n, m, (uint32_t *)(b + off_u), (uint32_t *)(b + off_v), (uint8_t *)(b + off_f), d_out[0],
-                                  d_out[1], d_out[2], pre ? d_out[3] : nullptr, size ? d_out[4] : nullptr, b + off_ws, ws,
-                                  st, result);
-  if (rc) return rc;
+  Staging s;
+  const auto d_u = s.take<uint32_t>(m), d_v = s.take<uint32_t>(m);
+  const auto d_f = s.take<uint8_t>(m);
   uint32_t *h_out[5] = {parent, parent_eid, depth, pre, size};
-  for (int k = 0; k < 5; ++k)
-    if (h_out[k]) GHS_HIP_CHECK(hipMemcpy(h_out[k], d_out[k], (size_t)n * 4, hipMemcpyDeviceToHost));
+  Staging::Piece<uint32_t> d_out[5];
+  for (auto &p : d_out) p = s.take<uint32_t>(n);
+  const auto d_ws = s.take<char>(ws);
+  GHS_HIP_CHECK(s.alloc());
+  hipStream_t st = nullptr;
+  GHS_HIP_CHECK(s.up(d_u, u, st));
+  GHS_HIP_CHECK(s.up(d_v, v, st));
+  GHS_HIP_CHECK(s.up(d_f, in_mst, st));
+  int rc = ghs_forest_root_device(n, m, s.at(d_u), s.at(d_v), s.at(d_f), s.at(d_out[0]), s.at(d_out[1]), s.at(d_out[2]),
+                                  s.at(d_out[3], pre), s.at(d_out[4], size), s.at(d_ws), ws, st, result);
+  if (rc) return rc;
+  for (int k = 0; k < 5; ++k) GHS_HIP_CHECK(s.down(h_out[k], d_out[k], n));
   return GHS_OK;
 }
+
+namespace {
+// What the path, replacement and distance forms share. root(): the edges and the flags on the device,
+// the flags rooted (ghs_forest_root_device without pre and size; flags that close a cycle are refused),
+// the index as the first piece of a second buffer, `ix`. The form then takes its own pieces from ix, and
+// index() allocates ix and builds the jump-pointer index. Public calls only.
+struct Rooted {
+  Staging in, ix;
+  Staging::Piece<uint32_t> u, v, w, parent, parent_eid, depth;
+  Staging::Piece<char> levels;
+  uint32_t n = 0;
+  uint64_t m = 0, max_depth = 0;
+  ghs_paths_t *h = nullptr;
+  ~Rooted() { (void)ghs_forest_paths_destroy(h); }
+  int root(uint32_t n_, uint64_t m_, const uint32_t *h_u, const uint32_t *h_v, const uint32_t *h_w, const uint8_t *in_mst,
+           hipStream_t st) {
+    n = n_, m = m_;
+    const size_t ws = m ? ghs_forest_root_workspace_bytes(n, m) : 0;
+    u = in.take<uint32_t>(m), v = in.take<uint32_t>(m), w = in.take<uint32_t>(m);
+    const auto f = in.take<uint8_t>(m);
+    parent = in.take<uint32_t>(n), parent_eid = in.take<uint32_t>(n), depth = in.take<uint32_t>(n);
+    const auto d_ws = in.take<char>(ws);
+    GHS_HIP_CHECK(in.alloc());
+    GHS_HIP_CHECK(in.up(u, h_u, st));
+    GHS_HIP_CHECK(in.up(v, h_v, st));
+    GHS_HIP_CHECK(in.up(w, h_w, st));
+    GHS_HIP_CHECK(in.up(f, in_mst, st));
+    ghs_root_result_t rr;
+    int rc = ghs_forest_root_device(n, m, in.at(u), in.at(v), in.at(f), in.at(parent), in.at(parent_eid), in.at(depth),
+                                    nullptr, nullptr, in.at(d_ws), ws, st, &rr);
+    if (rc) return rc;
+    if (!rr.is_forest) GHS_FAIL(GHS_E_ARG, "flags are not a forest");
+    max_depth = rr.max_depth;
+    levels = ix.take<char>(ghs_forest_paths_index_bytes(n, max_depth));
+    return GHS_OK;
+  }
+  int index(hipStream_t st) {
+    GHS_HIP_CHECK(ix.alloc());
+    ghs_paths_result_t pr;
+    return ghs_forest_paths_create(n, m, in.at(u), in.at(v), in.at(w), in.at(parent), in.at(parent_eid), in.at(depth),
+                                   max_depth, ix.at(levels), levels.count, st, &pr, &h);
+  }
+};
+}  // namespace
 
 // Host-buffer form of the path queries (what a reference user asks of a result by walking in_branch,
 // ghs_implementation.py:235-387): copy in, root the flags, build the jump-pointer index, query, copy out.
@@ -139,51 +160,23 @@ extern "C" int ghs_forest_paths_host(uint32_t n, uint64_t m, const uint32_t *u, 
   if (q == 0) return GHS_OK;
   result->queries = q;
   if (n == 0) GHS_FAIL(GHS_E_ARG, "vertex id out of range");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) GHS_FAIL(GHS_E_NODEVICE, "no HIP device");
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  if (int e = ghs::require_device()) return e;
   hipStream_t st = nullptr;
-  // stage 1: the edges, the flags, the rooted arrays, the rooting's workspace
-  const size_t ws = m ? ghs_forest_root_workspace_bytes(n, m) : 0;
-  const size_t nb = al((size_t)n * 4);
-  const size_t off_u = 0, off_v = off_u + al(m * 4), off_w = off_v + al(m * 4), off_f = off_w + al(m * 4),
-               off_o = off_f + al(m ? m : 1), off_ws = off_o + 3 * nb, total = off_ws + al(ws ? ws : 1);
-  DevBuf buf;
-  GHS_HIP_CHECK(hipMalloc(&buf.p, total));
-  char *d = (char *)buf.p;
-  if (m) {
-    GHS_HIP_CHECK(hipMemcpyAsync(d + off_u, u, m * 4, hipMemcpyHostToDevice, st));
-    GHS_HIP_CHECK(hipMemcpyAsync(d + off_v, v, m * 4, hipMemcpyHostToDevice, st));
-    GHS_HIP_CHECK(hipMemcpyAsync(d + off_w, w, m * 4, hipMemcpyHostToDevice, st));
-    GHS_HIP_CHECK(hipMemcpyAsync(d + off_f, in_mst, m, hipMemcpyHostToDevice, st));
-  }
-  uint32_t *d_par = (uint32_t *)(d + off_o), *d_peid = (uint32_t *)(d + off_o + nb), *d_dep = (uint32_t *)(d + off_o + 2 * nb);
-  ghs_root_result_t rr;
-  int rc = ghs_forest_root_device(n, m, (uint32_t *)(d + off_u), (uint32_t *)(d + off_v), (uint8_t *)(d + off_f), d_par,
-                                  d_peid, d_dep, nullptr, nullptr, d + off_ws, ws, st, &rr);
+  Rooted s;
+  if (int rc = s.root(n, m, u, v, w, in_mst, st)) return rc;
+  // next to the index: the pairs, the answers
+  const auto d_a = s.ix.take<uint32_t>(q), d_b = s.ix.take<uint32_t>(q);
+  const auto d_k = s.ix.take<uint64_t>(q);
+  const auto d_l = s.ix.take<uint32_t>(q), d_h = s.ix.take<uint32_t>(q);
+  if (int rc = s.index(st)) return rc;
+  GHS_HIP_CHECK(s.ix.up(d_a, a, st));
+  GHS_HIP_CHECK(s.ix.up(d_b, b, st));
+  int rc = ghs_forest_paths_query(s.h, q, s.ix.at(d_a), s.ix.at(d_b), s.ix.at(d_k, key), s.ix.at(d_l, lca), s.ix.at(d_h, hops),
+                                  st, result);
   if (rc) return rc;
-  if (!rr.is_forest) GHS_FAIL(GHS_E_ARG, "flags are not a forest");
-  // stage 2: the index, the pairs, the answers
-  const size_t ib = ghs_forest_paths_index_bytes(n, rr.max_depth);
-  const size_t qb = al(q * 4);
-  const size_t off_a = al(ib), off_b = off_a + qb, off_k = off_b + qb, off_l = off_k + al(q * 8), off_h = off_l + qb;
-  DevBuf ibuf;
-  GHS_HIP_CHECK(hipMalloc(&ibuf.p, off_h + qb));
-  char *x = (char *)ibuf.p;
-  GHS_HIP_CHECK(hipMemcpyAsync(x + off_a, a, q * 4, hipMemcpyHostToDevice, st));
-  GHS_HIP_CHECK(hipMemcpyAsync(x + off_b, b, q * 4, hipMemcpyHostToDevice, st));
-  ghs_paths_result_t pr;
-  ghs_paths_t *h = nullptr;
-  rc = ghs_forest_paths_create(n, m, (uint32_t *)(d + off_u), (uint32_t *)(d + off_v), (uint32_t *)(d + off_w), d_par, d_peid,
-                               d_dep, rr.max_depth, x, ib, st, &pr, &h);
-  if (rc) return rc;
-  rc = ghs_forest_paths_query(h, q, (uint32_t *)(x + off_a), (uint32_t *)(x + off_b), key ? (uint64_t *)(x + off_k) : nullptr,
-                              lca ? (uint32_t *)(x + off_l) : nullptr, hops ? (uint32_t *)(x + off_h) : nullptr, st, result);
-  (void)ghs_forest_paths_destroy(h);
-  if (rc) return rc;
-  if (key) GHS_HIP_CHECK(hipMemcpy(key, x + off_k, q * 8, hipMemcpyDeviceToHost));
-  if (lca) GHS_HIP_CHECK(hipMemcpy(lca, x + off_l, q * 4, hipMemcpyDeviceToHost));
-  if (hops) GHS_HIP_CHECK(hipMemcpy(hops, x + off_h, q * 4, hipMemcpyDeviceToHost));
+  GHS_HIP_CHECK(s.ix.down(key, d_k, q));
+  GHS_HIP_CHECK(s.ix.down(lca, d_l, q));
+  GHS_HIP_CHECK(s.ix.down(hops, d_h, q));
   return GHS_OK;
 }
 
@@ -199,47 +192,21 @@ extern "C" int ghs_forest_replace_host(uint32_t n, uint64_t m, const uint32_t *u
   if (m >= (1ull << 31)) GHS_FAIL(GHS_E_ARG, "m must be < 2^31");
   if (m && (!u || !v || !w || !in_mst)) GHS_FAIL(GHS_E_ARG, "NULL host pointer");
   if (n == 0) return GHS_OK;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) GHS_FAIL(GHS_E_NODEVICE, "no HIP device");
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  if (int e = ghs::require_device()) return e;
   hipStream_t st = nullptr;
-  // stage 1: the edges, the flags, the rooted arrays, the rooting's workspace
-  const size_t ws = m ? ghs_forest_root_workspace_bytes(n, m) : 0;
-  const size_t nb = al((size_t)n * 4);
-  const size_t off_u = 0, off_v = off_u + al(m * 4), off_w = off_v + al(m * 4), off_f = off_w + al(m * 4),
-               off_o = off_f + al(m ? m : 1), off_ws = off_o + 3 * nb, total = off_ws + al(ws ? ws : 1);
-  DevBuf buf;
-  GHS_HIP_CHECK(hipMalloc(&buf.p, total));
-  char *d = (char *)buf.p;
-  if (m) {
-    GHS_HIP_CHECK(hipMemcpyAsync(d + off_u, u, m * 4, hipMemcpyHostToDevice, st));
-    GHS_HIP_CHECK(hipMemcpyAsync(d + off_v, v, m * 4, hipMemcpyHostToDevice, st));
-    GHS_HIP_CHECK(hipMemcpyAsync(d + off_w, w, m * 4, hipMemcpyHostToDevice, st));
-    GHS_HIP_CHECK(hipMemcpyAsync(d + off_f, in_mst, m, hipMemcpyHostToDevice, st));
-  }
-  uint32_t *d_u = (uint32_t *)(d + off_u), *d_v = (uint32_t *)(d + off_v), *d_w = (uint32_t *)(d + off_w);
-  uint32_t *d_par = (uint32_t *)(d + off_o), *d_peid = (uint32_t *)(d + off_o + nb), *d_dep = (uint32_t *)(d + off_o + 2 * nb);
-  ghs_root_result_t rr;
-  int rc = ghs_forest_root_device(n, m, d_u, d_v, (uint8_t *)(d + off_f), d_par, d_peid, d_dep, nullptr, nullptr, d + off_ws,
-                                  ws, st, &rr);
+  Rooted s;
+  if (int rc = s.root(n, m, u, v, w, in_mst, st)) return rc;
+  // next to the index: the cover levels, the answers
+  const size_t rb = ghs_forest_replace_workspace_bytes(n, s.max_depth);
+  const auto d_ws = s.ix.take<char>(rb);
+  const auto d_r = s.ix.take<uint64_t>(n);
+  const auto d_e = s.ix.take<uint32_t>(m);
+  if (int rc = s.index(st)) return rc;
+  int rc = ghs_forest_replace_device(s.h, m, s.in.at(s.u), s.in.at(s.v), s.in.at(s.w), s.ix.at(d_r),
+                                     s.ix.at(d_e, m ? repl_eid_by_edge : nullptr), s.ix.at(d_ws), rb, st, result);
   if (rc) return rc;
-  if (!rr.is_forest) GHS_FAIL(GHS_E_ARG, "flags are not a forest");
-  // stage 2: the index, the cover levels, the answers
-  const size_t ib = ghs_forest_paths_index_bytes(n, rr.max_depth), rb = ghs_forest_replace_workspace_bytes(n, rr.max_depth);
-  const size_t off_rws = al(ib), off_r = off_rws + al(rb), off_e = off_r + al((size_t)n * 8);
-  DevBuf ibuf;
-  GHS_HIP_CHECK(hipMalloc(&ibuf.p, off_e + al(m ? m * 4 : 1)));
-  char *x = (char *)ibuf.p;
-  ghs_paths_result_t pr;
-  ghs_paths_t *h = nullptr;
-  rc = ghs_forest_paths_create(n, m, d_u, d_v, d_w, d_par, d_peid, d_dep, rr.max_depth, x, ib, st, &pr, &h);
-  if (rc) return rc;
-  rc = ghs_forest_replace_device(h, m, d_u, d_v, d_w, (uint64_t *)(x + off_r),
-                                 repl_eid_by_edge && m ? (uint32_t *)(x + off_e) : nullptr, x + off_rws, rb, st, result);
-  (void)ghs_forest_paths_destroy(h);
-  if (rc) return rc;
-  if (repl) GHS_HIP_CHECK(hipMemcpy(repl, x + off_r, (size_t)n * 8, hipMemcpyDeviceToHost));
-  if (repl_eid_by_edge && m) GHS_HIP_CHECK(hipMemcpy(repl_eid_by_edge, x + off_e, m * 4, hipMemcpyDeviceToHost));
+  GHS_HIP_CHECK(s.ix.down(repl, d_r, n));
+  GHS_HIP_CHECK(s.ix.down(repl_eid_by_edge, d_e, m));
   return GHS_OK;
 }
 
@@ -247,49 +214,16 @@ extern "C" int ghs_forest_replace_host(uint32_t n, uint64_t m, const uint32_t *u
 // the weights up, ghs_implementation.py:63,212): copy in, root the flags, build the jump-pointer index
 // and the weighted depth, answer, copy out. Public calls only.
 namespace {
-// what both forms share: the edges and flags on the device, the rooted arrays, the index, the weighted depth
-struct DistStage {
-  DevBuf buf, ibuf;
-  ghs_paths_t *h = nullptr;
-  uint64_t *d_wd = nullptr;
-  char *extra = nullptr;  // extra_bytes for the caller, 256-byte aligned
-  void *d_ws = nullptr;   // the dist workspace (scratch again after run)
-  size_t ws_bytes = 0;
-  ~DistStage() { (void)ghs_forest_paths_destroy(h); }
-  int run(uint32_t n, uint64_t m, const uint32_t *u, const uint32_t *v, const uint32_t *w, const uint8_t *in_mst,
-          uint32_t metric, size_t extra_bytes, hipStream_t st) {
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t ws = m ? ghs_forest_root_workspace_bytes(n, m) : 0;
-    const size_t nb = al((size_t)n * 4);
-    const size_t off_u = 0, off_v = off_u + al(m * 4), off_w = off_v + al(m * 4), off_f = off_w + al(m * 4),
-                 off_o = off_f + al(m ? m : 1), off_ws = off_o + 3 * nb, total = off_ws + al(ws ? ws : 1);
-    GHS_HIP_CHECK(hipMalloc(&buf.p, total));
-    char *d = (char *)buf.p;
-    if (m) {
-      GHS_HIP_CHECK(hipMemcpyAsync(d + off_u, u, m * 4, hipMemcpyHostToDevice, st));
-      GHS_HIP_CHECK(hipMemcpyAsync(d + off_v, v, m * 4, hipMemcpyHostToDevice, st));
-      GHS_HIP_CHECK(hipMemcpyAsync(d + off_w, w, m * 4, hipMemcpyHostToDevice, st));
-      GHS_HIP_CHECK(hipMemcpyAsync(d + off_f, in_mst, m, hipMemcpyHostToDevice, st));
-    }
-    uint32_t *d_u = (uint32_t *)(d + off_u), *d_v = (uint32_t *)(d + off_v), *d_w = (uint32_t *)(d + off_w);
-    uint32_t *d_par = (uint32_t *)(d + off_o), *d_peid = (uint32_t *)(d + off_o + nb), *d_dep = (uint32_t *)(d + off_o + 2 * nb);
-    ghs_root_result_t rr;
-    int rc = ghs_forest_root_device(n, m, d_u, d_v, (uint8_t *)(d + off_f), d_par, d_peid, d_dep, nullptr, nullptr, d + off_ws,
-                                    ws, st, &rr);
-    if (rc) return rc;
-    if (!rr.is_forest) GHS_FAIL(GHS_E_ARG, "flags are not a forest");
-    const size_t ib = ghs_forest_paths_index_bytes(n, rr.max_depth);
-    ws_bytes = ghs_forest_dist_workspace_bytes(n, rr.max_depth);
-    const size_t off_dws = al(ib), off_wd = off_dws + al(ws_bytes), off_x = off_wd + al((size_t)n * 8);
-    GHS_HIP_CHECK(hipMalloc(&ibuf.p, off_x + al(extra_bytes ? extra_bytes : 1)));
-    char *x = (char *)ibuf.p;
-    ghs_paths_result_t pr;
-    rc = ghs_forest_paths_create(n, m, d_u, d_v, d_w, d_par, d_peid, d_dep, rr.max_depth, x, ib, st, &pr, &h);
-    if (rc) return rc;
-    d_ws = x + off_dws;
-    d_wd = (uint64_t *)(x + off_wd);
-    extra = x + off_x;
-    return ghs_forest_wdepth_device(h, metric, d_wd, d_ws, ws_bytes, st);
+// what both forms share on top of the rooted stage: the dist workspace and the weighted depth next to the index
+struct DistStage : Rooted {
+  Staging::Piece<char> ws;  // the dist workspace (scratch again after depths())
+  Staging::Piece<uint64_t> wdepth;
+  // root(), then the form's own pieces from ix, then depths()
+  int depths(uint32_t metric, hipStream_t st) {
+    ws = ix.take<char>(ghs_forest_dist_workspace_bytes(n, max_depth));
+    wdepth = ix.take<uint64_t>(n);
+    if (int rc = index(st)) return rc;
+    return ghs_forest_wdepth_device(h, metric, ix.at(wdepth), ix.at(ws), ws.count, st);
   }
 };
 }  // namespace
@@ -306,22 +240,21 @@ extern "C" int ghs_forest_dist_host(uint32_t n, uint64_t m, const uint32_t *u, c
   if (q == 0) return GHS_OK;
   result->queries = q;
   if (n == 0) GHS_FAIL(GHS_E_ARG, "vertex id out of range");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) GHS_FAIL(GHS_E_NODEVICE, "no HIP device");
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  if (int e = ghs::require_device()) return e;
   hipStream_t st = nullptr;
-  const size_t qb = al(q * 4);
-  const size_t off_a = 0, off_b = off_a + qb, off_d = off_b + qb, off_l = off_d + al(q * 8);
   DistStage s;
-  if (int rc = s.run(n, m, u, v, w, in_mst, metric, off_l + qb, st)) return rc;
-  char *x = s.extra;
-  GHS_HIP_CHECK(hipMemcpyAsync(x + off_a, a, q * 4, hipMemcpyHostToDevice, st));
-  GHS_HIP_CHECK(hipMemcpyAsync(x + off_b, b, q * 4, hipMemcpyHostToDevice, st));
-  int rc = ghs_forest_dist_query(s.h, s.d_wd, q, (uint32_t *)(x + off_a), (uint32_t *)(x + off_b), (uint64_t *)(x + off_d),
-                                 lca ? (uint32_t *)(x + off_l) : nullptr, result, st);
+  if (int rc = s.root(n, m, u, v, w, in_mst, st)) return rc;
+  const auto d_a = s.ix.take<uint32_t>(q), d_b = s.ix.take<uint32_t>(q);
+  const auto d_d = s.ix.take<uint64_t>(q);
+  const auto d_l = s.ix.take<uint32_t>(q);
+  if (int rc = s.depths(metric, st)) return rc;
+  GHS_HIP_CHECK(s.ix.up(d_a, a, st));
+  GHS_HIP_CHECK(s.ix.up(d_b, b, st));
+  int rc = ghs_forest_dist_query(s.h, s.ix.at(s.wdepth), q, s.ix.at(d_a), s.ix.at(d_b), s.ix.at(d_d), s.ix.at(d_l, lca), result,
+                                 st);
   if (rc) return rc;
-  if (dist) GHS_HIP_CHECK(hipMemcpy(dist, x + off_d, q * 8, hipMemcpyDeviceToHost));
-  if (lca) GHS_HIP_CHECK(hipMemcpy(lca, x + off_l, q * 4, hipMemcpyDeviceToHost));
+  GHS_HIP_CHECK(s.ix.down(dist, d_d, q));
+  GHS_HIP_CHECK(s.ix.down(lca, d_l, q));
   return GHS_OK;
 }
 
@@ -335,23 +268,20 @@ extern "C" int ghs_forest_diameter_host(uint32_t n, uint64_t m, const uint32_t *
   if (m >= (1ull << 31)) GHS_FAIL(GHS_E_ARG, "m must be < 2^31");
   if (m && (!u || !v || !w || !in_mst)) GHS_FAIL(GHS_E_ARG, "NULL host pointer");
   if (n == 0) return GHS_OK;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) GHS_FAIL(GHS_E_NODEVICE, "no HIP device");
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  if (int e = ghs::require_device()) return e;
   hipStream_t st = nullptr;
-  const size_t nb4 = al((size_t)n * 4), nb8 = al((size_t)n * 8);
-  const size_t off_r = 0, off_a = off_r + nb4, off_b = off_a + nb4, off_d = off_b + nb4, off_e = off_d + nb8;
   DistStage s;
-  if (int rc = s.run(n, m, u, v, w, in_mst, metric, off_e + nb8, st)) return rc;
-  char *x = s.extra;
-  int rc = ghs_forest_diameter_device(s.h, s.d_wd, (uint32_t *)(x + off_r), (uint64_t *)(x + off_d), (uint32_t *)(x + off_a),
-                                      (uint32_t *)(x + off_b), ecc ? (uint64_t *)(x + off_e) : nullptr, s.d_ws, s.ws_bytes,
-                                      result, st);
+  if (int rc = s.root(n, m, u, v, w, in_mst, st)) return rc;
+  const auto d_r = s.ix.take<uint32_t>(n), d_a = s.ix.take<uint32_t>(n), d_b = s.ix.take<uint32_t>(n);
+  const auto d_d = s.ix.take<uint64_t>(n), d_e = s.ix.take<uint64_t>(n);
+  if (int rc = s.depths(metric, st)) return rc;
+  int rc = ghs_forest_diameter_device(s.h, s.ix.at(s.wdepth), s.ix.at(d_r), s.ix.at(d_d), s.ix.at(d_a), s.ix.at(d_b),
+                                      s.ix.at(d_e, ecc), s.ix.at(s.ws), s.ws.count, result, st);
   if (rc) return rc;
-  if (root_of) GHS_HIP_CHECK(hipMemcpy(root_of, x + off_r, (size_t)n * 4, hipMemcpyDeviceToHost));
-  if (diam) GHS_HIP_CHECK(hipMemcpy(diam, x + off_d, (size_t)n * 8, hipMemcpyDeviceToHost));
-  if (end_a) GHS_HIP_CHECK(hipMemcpy(end_a, x + off_a, (size_t)n * 4, hipMemcpyDeviceToHost));
-  if (end_b) GHS_HIP_CHECK(hipMemcpy(end_b, x + off_b, (size_t)n * 4, hipMemcpyDeviceToHost));
-  if (ecc) GHS_HIP_CHECK(hipMemcpy(ecc, x + off_e, (size_t)n * 8, hipMemcpyDeviceToHost));
+  GHS_HIP_CHECK(s.ix.down(root_of, d_r, n));
+  GHS_HIP_CHECK(s.ix.down(diam, d_d, n));
+  GHS_HIP_CHECK(s.ix.down(end_a, d_a, n));
+  GHS_HIP_CHECK(s.ix.down(end_b, d_b, n));
+  GHS_HIP_CHECK(s.ix.down(ecc, d_e, n));
   return GHS_OK;
 }

@@ -709,36 +709,22 @@ int ghs_mutual_reach_host(uint32_t n, uint64_t m, const uint32_t *u, const uint3
   *result = ghs_mreach_result_t{};
   if (int e = check_args(n, m, u, v, w, k, core, w_out, false, nullptr, 0)) return e;
   if (n == 0) return GHS_OK;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) GHS_FAIL(GHS_E_NODEVICE, "no HIP device");
-  const size_t ws = ghs_mutual_reach_workspace_bytes(n, m), mb = (size_t)m * 4, nb = (size_t)n * 4;
-  size_t o = 0;
-  auto take = [&o](size_t bytes) {
-    const size_t at = o;
-    o += align256(bytes ? bytes : 1);
-    return at;
-  };
-  const size_t i_u = take(mb), i_v = take(mb), i_w = take(mb), o_core = take(nb), o_w = take(mb), o_ws = take(ws);
-  struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() {
-      if (p) (void)hipFree(p);
-    }
-  } buf;
-  GHS_HIP_CHECK(hipMalloc(&buf.p, o));
-  char *b = (char *)buf.p;
+  if (int e = ghs::require_device()) return e;
+  const size_t ws = ghs_mutual_reach_workspace_bytes(n, m);
+  ghs::Staging s;
+  const auto i_u = s.take<uint32_t>(m), i_v = s.take<uint32_t>(m), i_w = s.take<uint32_t>(m);
+  const auto o_core = s.take<uint32_t>(n), o_w = s.take<uint32_t>(m);
+  const auto d_ws = s.take<char>(ws);
+  GHS_HIP_CHECK(s.alloc());
   hipStream_t st = nullptr;
-  if (m) {
-    GHS_HIP_CHECK(hipMemcpyAsync(b + i_u, u, mb, hipMemcpyHostToDevice, st));
-    GHS_HIP_CHECK(hipMemcpyAsync(b + i_v, v, mb, hipMemcpyHostToDevice, st));
-    GHS_HIP_CHECK(hipMemcpyAsync(b + i_w, w, mb, hipMemcpyHostToDevice, st));
-  }
-  const int rc = ghs_mutual_reach_device(n, m, (uint32_t *)(b + i_u), (uint32_t *)(b + i_v), (uint32_t *)(b + i_w), k,
-                                         (uint32_t *)(b + o_core), w_out ? (uint32_t *)(b + o_w) : nullptr, b + o_ws, ws, st,
-                                         result);
+  GHS_HIP_CHECK(s.up(i_u, u, st));
+  GHS_HIP_CHECK(s.up(i_v, v, st));
+  GHS_HIP_CHECK(s.up(i_w, w, st));
+  const int rc = ghs_mutual_reach_device(n, m, s.at(i_u), s.at(i_v), s.at(i_w), k, s.at(o_core), s.at(o_w, w_out), s.at(d_ws),
+                                         ws, st, result);
   if (rc) return rc;
-  GHS_HIP_CHECK(hipMemcpy(core, b + o_core, nb, hipMemcpyDeviceToHost));
-  if (w_out && m) GHS_HIP_CHECK(hipMemcpy(w_out, b + o_w, mb, hipMemcpyDeviceToHost));
+  GHS_HIP_CHECK(s.down(core, o_core, n));
+  GHS_HIP_CHECK(s.down(w_out, o_w, m));
   return GHS_OK;
 }
 
