@@ -34,17 +34,20 @@ the weights HDBSCAN wants (core distances: the min_samples-th smallest weight at
 reachability: max(core[u], core[v], w) on every edge) and HDBSCAN end to end on a k-NN graph or a
 sparse distance matrix: device.mutual_reachability, DeviceEdges.mutual_reachability, device.hdbscan,
 DeviceEdges.hdbscan, mst.hdbscan_edges, CLI --mutual-reachability OUT.npz, --hdbscan OUT.npz;
+where the graph comes from (the exact brute-force k nearest neighbours of float32 points, the symmetrised
+k-NN graph as a canonical list, HDBSCAN from points end to end): device.knn, device.knn_graph,
+device.hdbscan_points, mst.hdbscan_points, CLI --points X.npy --knn K --knn-graph OUT.npz / --hdbscan OUT.npz;
 multi-GPU: distributed.DistributedMST. Float, negative and 64-bit
 weights: rank-mapped by graph.canonicalize on the host, or on the device with rank_weights=True
 (minimum_spanning_forest_edges, DeviceEdges.from_raw, canonicalize_device; device.weight_ranks).
 """
 from .graph import (CanonicalGraph, canonicalize, read_graph_dir, read_mstbin, write_graph_dir, write_mstbin,
                     write_result)
-from .mst import (GHSAlgorithm, MSTResult, hdbscan_edges, minimum_spanning_forest, minimum_spanning_forest_batch,
+from .mst import (GHSAlgorithm, MSTResult, hdbscan_edges, hdbscan_points, minimum_spanning_forest, minimum_spanning_forest_batch,
                   minimum_spanning_forest_edges)
 
 __all__ = [
     "CanonicalGraph", "canonicalize", "read_graph_dir", "read_mstbin", "write_graph_dir", "write_mstbin",
     "write_result", "GHSAlgorithm", "MSTResult", "minimum_spanning_forest", "minimum_spanning_forest_batch",
-    "minimum_spanning_forest_edges", "hdbscan_edges",
+    "minimum_spanning_forest_edges", "hdbscan_edges", "hdbscan_points",
 ]

@@ -159,6 +159,45 @@ def run_batch_dir(args):
     return 1 if (args.check and bad) else 0
 
 
+def run_points(args):
+    """--points X.npy: the k-NN graph (--knn-graph) and / or HDBSCAN from points (--hdbscan)."""
+    import numpy as np
+
+    t0 = time.perf_counter()
+    X = np.load(args.points)
+    t_read = time.perf_counter() - t0
+    metric = args.metric or "euclidean"
+    if args.knn_graph is not None:
+        import torch
+
+        from .device import knn_graph
+        if X.ndim != 2 or X.dtype == np.float64:
+            raise ValueError("--points: an (n, d) array of float32 / float16 / integer points expected "
+                             "(float64 is never narrowed silently)")
+        g = knn_graph(torch.from_numpy(np.ascontiguousarray(X if X.dtype.kind != "u" else X.astype(np.int64))).to("cuda"),
+                      args.knn, metric=metric)
+        e = g.edges
+        np.savez(args.knn_graph, idx=g.knn.idx.cpu().numpy().view(np.uint32), dist=g.knn.dist.cpu().numpy(),
+                 u=e.u.cpu().numpy().view(np.uint32), v=e.v.cpu().numpy().view(np.uint32), w=e.weights.cpu().numpy())
+        if not args.quiet:
+            print(f"Points: {X.shape[0]} x {X.shape[1]}  k = {args.knn}  k-NN graph edges: {e.m}  "
+                  f"zero distances: {g.knn.info['zero_neighbours']}  knn: {g.knn.info['ms_total']:.3f} ms  "
+                  f"read: {t_read * 1e3:.1f} ms")
+            print(f"k-NN graph saved to: {args.knn_graph}")
+    if args.hdbscan is not None:
+        from .mst import hdbscan_points
+        mcs = 5 if args.min_cluster_size is None else args.min_cluster_size
+        out, info = hdbscan_points(X, min_cluster_size=mcs, min_samples=args.min_samples, k=args.knn, metric=metric,
+                                   method=args.cluster_method, allow_single_cluster=args.allow_single_cluster,
+                                   return_info=True)
+        np.savez(args.hdbscan, **out)
+        if not args.quiet:
+            print(f"HDBSCAN from points: {info['cluster']['num_selected']} clusters, {info['cluster']['num_noise']} noise "
+                  f"points of {X.shape[0]} (k = {info['knn']['k']}, {metric})")
+            print(f"HDBSCAN saved to: {args.hdbscan}")
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="MI355X Boruvka MST (drop-in for ghs_implementation_mpi.py)")
     ap.add_argument("--batch-dir", type=str, default=None,
@@ -216,6 +255,15 @@ def main(argv=None):
     ap.add_argument("--stretch", type=str, default=None, metavar="OUT.npz",
                     help="write the forest distance of every graph edge (dist) and the stretch summary after the solve")
     ap.add_argument("--hops", action="store_true", help="with --distances / --diameters: count edges, not weights")
+    ap.add_argument("--points", type=str, default=None, metavar="X.npy",
+                    help="an (n, d) array of points instead of a graph (float32 / float16 / integers): the exact k-NN "
+                         "graph is built on the device; takes --knn, --metric, --knn-graph and --hdbscan")
+    ap.add_argument("--knn", type=int, default=None, metavar="K",
+                    help="with --points: neighbours per point (default with --hdbscan: --min-samples)")
+    ap.add_argument("--metric", choices=["euclidean", "sqeuclidean"], default=None,
+                    help="with --points: the distance written and clustered on (default euclidean)")
+    ap.add_argument("--knn-graph", type=str, default=None, metavar="OUT.npz",
+                    help="with --points: write the k-NN table (idx, dist) and the symmetrised canonical graph (u, v, w)")
     ap.add_argument("--gpus", type=int, default=1, help="GPUs driven by this one process (RCCL clique)")
     ap.add_argument("--generator", choices=["rmat", "grid"], default=None, help="synthetic graph instead of a file")
     ap.add_argument("--scale", type=int, default=16, help="R-MAT scale (2^scale vertices) / grid side k")
@@ -246,6 +294,22 @@ def main(argv=None):
         ap.error("--paths OUT.npz and --pairs PAIRS.npy go together")
     if args.distances is not None and args.pairs is None:
         ap.error("--distances OUT.npz needs --pairs PAIRS.npy")
+    if args.points is None and (args.knn is not None or args.metric is not None or args.knn_graph is not None):
+        ap.error("--knn / --metric / --knn-graph need --points X.npy")
+    if args.points is not None:
+        if args.graph is not None or args.generator is not None or args.batch_dir is not None:
+            ap.error("--points excludes --graph, --generator and --batch-dir")
+        if args.knn_graph is None and args.hdbscan is None:
+            ap.error("--points X.npy needs --knn-graph OUT.npz or --hdbscan OUT.npz")
+        if args.knn is not None and not 1 <= args.knn <= 128:
+            ap.error("--knn K needs 1 <= K <= 128")
+        if args.knn_graph is not None and args.knn is None:
+            ap.error("--knn-graph OUT.npz needs --knn K")
+        others = ("labels", "cluster_out", "clusters", "mutual_reachability", "rooted", "dendrogram", "paths",
+                  "replacements", "distances", "diameters", "stretch", "check_result")
+        if any(getattr(args, o) is not None for o in others) or args.check or args.check_device:
+            ap.error("--points takes --knn-graph OUT.npz and --hdbscan OUT.npz only (the graph outputs need a graph)")
+        return run_points(args)
     if args.batch_dir is not None:
         return run_batch_dir(args)
 

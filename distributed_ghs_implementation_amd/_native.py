@@ -76,6 +76,7 @@ EXPORTED_SYMBOLS = (
     "ghs_forest_cluster_workspace_bytes", "ghs_forest_cluster_capacity", "ghs_forest_cluster_device",
     "ghs_forest_cluster_host",
     "ghs_mutual_reach_workspace_bytes", "ghs_mutual_reach_device", "ghs_mutual_reach_host", "ghs_mutual_reach_phases",
+    "ghs_knn_workspace_bytes", "ghs_knn_device", "ghs_knn_host",
 )
 
 
@@ -315,6 +316,62 @@ def mreach_args(min_samples, short_rows, include_self=False):
     if short_rows not in ("error", "clamp"):
         raise ValueError(f"short_rows: 'error' or 'clamp' expected, got {short_rows!r}")
     return k - 1 if include_self else k
+
+
+# ghs_knn_device's limits, metrics and tile shape (include/ghs_mst.h GHS_KNN_*)
+GHS_KNN_MAX_K = 128
+GHS_KNN_MAX_DIM = 4096
+GHS_KNN_MAX_SLICES = 64
+GHS_KNN_SQEUCLIDEAN = 0
+GHS_KNN_EUCLIDEAN = 1
+GHS_KNN_TILE_Q = 64
+GHS_KNN_TILE_C = 64
+GHS_KNN_DIM_CHUNK = 32
+KNN_METRICS = {"sqeuclidean": GHS_KNN_SQEUCLIDEAN, "euclidean": GHS_KNN_EUCLIDEAN}
+
+
+class KnnResult(ctypes.Structure):
+    """ghs_knn_result_t: what ghs_knn_device / ghs_knn_host found."""
+    _fields_ = [
+        ("pairs", ctypes.c_uint64),
+        ("zero_neighbours", ctypes.c_uint64),
+        ("slices", ctypes.c_uint32),
+        ("query_tiles", ctypes.c_uint32),
+        ("ms_total", ctypes.c_double),
+        ("reserved", ctypes.c_uint64 * 2),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+def knn_args(k, metric, slices=0, n=None, dim=None):
+    """(k, metric code, slices) of the k-NN entry points; ValueError for what they would refuse, before
+    anything touches the device. n, dim: the points' shape when it is known."""
+    try:
+        kk = int(k)
+    except (TypeError, ValueError):
+        raise ValueError(f"k must be an integer in [1, {GHS_KNN_MAX_K}], got {k!r}") from None
+    if kk != k or not 1 <= kk <= GHS_KNN_MAX_K:
+        raise ValueError(f"k must be an integer in [1, {GHS_KNN_MAX_K}], got {k!r}")
+    if metric not in KNN_METRICS:
+        raise ValueError(f"metric: 'euclidean' or 'sqeuclidean' expected, got {metric!r}")
+    try:
+        ss = int(slices)
+    except (TypeError, ValueError):
+        raise ValueError(f"slices must be an integer in [0, {GHS_KNN_MAX_SLICES}] (0: chosen from n), got {slices!r}") from None
+    if ss != slices or not 0 <= ss <= GHS_KNN_MAX_SLICES:
+        raise ValueError(f"slices must be an integer in [0, {GHS_KNN_MAX_SLICES}] (0: chosen from n), got {slices!r}")
+    if dim is not None and not 1 <= int(dim) <= GHS_KNN_MAX_DIM:
+        raise ValueError(f"points must have between 1 and {GHS_KNN_MAX_DIM} columns, got {dim}")
+    if n is not None:
+        if int(n) >= (1 << 32):
+            raise ValueError("at most 2^32 - 1 points")
+        if int(n) >= 1 and kk > int(n) - 1:
+            raise ValueError(f"k = {kk} needs at least k + 1 points (a point is not its own neighbour), got n = {n}")
+        if int(n) * kk >= (1 << 32):
+            raise ValueError("n * k must be < 2^32")
+    return kk, KNN_METRICS[metric], ss
 
 
 class PathsResult(ctypes.Structure):
@@ -665,6 +722,10 @@ def load():
             "ghs_mutual_reach_device": (i32, [u32, u64, vp, vp, vp, u32, vp, vp, vp, sz, vp, P(MreachResult)]),
             "ghs_mutual_reach_host": (i32, [u32, u64, vp, vp, vp, u32, vp, vp, P(MreachResult)]),
             "ghs_mutual_reach_phases": (i32, [i32, P(ctypes.c_double)]),
+            # ABI 10 addition: exact brute-force k nearest neighbours of float32 points
+            "ghs_knn_workspace_bytes": (sz, [u32, u32, u32, u32]),
+            "ghs_knn_device": (i32, [u32, u32, vp, u32, u32, u32, vp, vp, vp, sz, vp, P(KnnResult)]),
+            "ghs_knn_host": (i32, [u32, u32, vp, u32, u32, vp, vp, P(KnnResult)]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(L, name)

@@ -1040,6 +1040,145 @@ def hdbscan(edges, min_cluster_size=5, min_samples=None, method="eom", allow_sin
     return HDBSCANResult(reach, mst, dg, cl)
 
 
+class KNN:
+    """What `knn` found. idx: (n, k) int32 GPU tensor of uint32 bits, row i the neighbours of point i in
+    ascending (distance, index) order; dist: (n, k) float32, their distances (squared for
+    metric="sqeuclidean"); info: the fields of ghs_knn_result_t as a dict, plus k and metric."""
+
+    def __init__(self, idx, dist, info=None):
+        self.idx, self.dist, self.info = idx, dist, info
+
+
+class KNNGraph:
+    """What `knn_graph` built. edges: the canonical DeviceEdges of the symmetrised k-NN graph (`w` the
+    ranks of the distances, `weights` the float32 distances, `src` the index into the flattened (n, k)
+    table); knn: the KNN it came from."""
+
+    def __init__(self, edges, knn):
+        self.edges, self.knn = edges, knn
+
+
+_INT_POINT_TYPES = (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
+
+
+def _points_f32(points):
+    """points as a contiguous float32 GPU matrix: float32 as it is, float16 / bfloat16 widened (exact),
+    integers when every |x| < 2^24 (exact; checked on the device). ValueError for anything else; float64
+    is never narrowed silently. Everything that needs no device comes first."""
+    if not (isinstance(points, torch.Tensor) and points.dim() == 2):
+        raise ValueError("points: a two-dimensional (n, d) GPU tensor expected")
+    if points.dtype == torch.float64:
+        raise ValueError("points: float64 is never narrowed silently; cast with points.to(torch.float32) "
+                         "if float32 distances are what you want")
+    if points.dtype not in (torch.float32, torch.float16, torch.bfloat16) + _INT_POINT_TYPES:
+        raise ValueError(f"points: float32 / float16 / bfloat16 or an integer tensor expected, got {points.dtype}")
+    return points
+
+
+def knn(points, k, metric="euclidean", slices=0):
+    """The exact k nearest neighbours of every row of `points`, by brute force on the device
+    (ghs_knn_device, csrc/knn.hip). points: a 2-D GPU tensor (n, d), d <= 4096; float32 is used as it is
+    (made contiguous if needed), float16 / bfloat16 are widened to float32 and integer dtypes converted
+    when every |x| < 2^24 (both exact; ValueError otherwise); float64 raises ValueError: cast it yourself.
+    1 <= k <= min(128, n - 1). metric: "euclidean" or "sqeuclidean".
+    Exact means: the squared distance is the float32 chain s = a[t] - b[t], acc = fmaf(s, s, acc) over
+    t ascending (relative error at most (d + 3) * 2^-23, symmetric bit for bit, 0 for equal rows), the
+    neighbours of i are the k points j != i with the smallest (that value, j), ties to the smaller index,
+    and "euclidean" is its correctly rounded square root. A duplicate of a point is its neighbour at
+    distance 0 (info["zero_neighbours"] counts such entries). The same bytes on every call and for every
+    `slices` (0: chosen from n; a tuning knob only). Runs on torch's current stream; a NaN or infinite
+    coordinate raises GHSError (GHS_E_ARG). Returns a `KNN` (idx, dist, info)."""
+    points = _points_f32(points)
+    n, dim = int(points.shape[0]), int(points.shape[1])
+    kk, mcode, ss = _native.knn_args(k, metric, slices, n=n, dim=dim)
+    L = _native.load()
+    _native.require_gpu()
+    if not points.is_cuda:
+        raise ValueError("points: a two-dimensional (n, d) GPU tensor expected")
+    dev = points.device
+    with torch.cuda.device(dev):
+        if points.dtype in (torch.int32, torch.int64) and points.numel():  # the narrower ones cannot reach 2^24
+            if bool(((points >= (1 << 24)) | (points <= -(1 << 24))).any()):
+                raise ValueError("points: integer coordinates must satisfy |x| < 2^24 to be exact in float32")
+        x = points.to(torch.float32).contiguous()
+        if x.data_ptr() % 16:
+            x = x.clone()  # a view that starts off a 16-byte boundary
+        idx = torch.empty((n, kk), dtype=torch.int32, device=dev)
+        dist = torch.empty((n, kk), dtype=torch.float32, device=dev)
+        res = _native.KnnResult()
+        ws_bytes = int(L.ghs_knn_workspace_bytes(n, dim, kk, ss))
+        ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=dev)
+        _native.check(L.ghs_knn_device(n, dim, _ptr(x), kk, mcode, ss, _ptr(idx), _ptr(dist), _ptr(ws), ws_bytes, _stream(),
+                                       ctypes.byref(res)))
+        del ws
+    info = res.as_dict()
+    info["k"], info["metric"] = kk, metric
+    return KNN(idx, dist, info)
+
+
+def knn_graph(points, k, metric="euclidean"):
+    """The symmetrised k-NN graph of `points` as a canonical edge list, without leaving the device: `knn`,
+    then the raw edges (i, idx[i, j], dist[i, j]) through `canonicalize_device(..., rank_weights=True)`.
+    edges.w holds the ranks of the distances, edges.weights the float32 distances and edges.src the index
+    into the flattened (n, k) table; n * k / 2 <= m <= n * k. Every vertex has degree >= k. Returns a
+    `KNNGraph` (edges, knn)."""
+    nn = knn(points, k, metric=metric)
+    n, kk = int(nn.idx.shape[0]), int(nn.idx.shape[1])
+    dev = nn.idx.device
+    with torch.cuda.device(dev):
+        # the row ids are plumbing: no kernel of ours
+        ru = torch.arange(n, dtype=torch.int32, device=dev).repeat_interleave(kk)
+        # A pair that both ends chose appears twice, as (i, j) and as (j, i). The ingest keeps the last
+        # occurrence; the squared distance is symmetric bit for bit (and so is its square root), so both
+        # occurrences carry the same weight and which one wins cannot matter.
+        edges = canonicalize_device(n, ru, nn.idx.reshape(-1), nn.dist.reshape(-1), rank_weights=True)
+    return KNNGraph(edges, nn)
+
+
+def hdbscan_points(points, min_cluster_size=5, min_samples=None, k=None, metric="euclidean", method="eom",
+                   allow_single_cluster=False):
+    """HDBSCAN of points end to end on the device: `knn_graph(points, k)` -> `hdbscan(edges, ...,
+    include_self=True, short_rows="error")`. include_self=True is scikit-learn's convention for points (a
+    point is its own first neighbour), min_samples=None means min_cluster_size, k=None means
+    max(1, min_samples). k < max(1, min_samples - 1) or k > n - 1 raises ValueError.
+    What is exact: the core distances. Row x of the symmetrised graph holds x's own k nearest plus the
+    points that chose x; a point that chose x without being among x's k nearest is no nearer than x's
+    k-th; so the (min_samples - 1)-th smallest of the row is the true one whenever k >= min_samples - 1:
+    the cores equal those of the dense definition.
+    What is not exact: the forest. It is the minimum spanning forest of the k-NN graph under the
+    mutual-reachability weights. It equals the MST of the complete mutual-reachability graph exactly when
+    that MST uses edges of the k-NN graph only, which is certain at k = n - 1 and likely for k well above
+    min_samples; otherwise the forest has several trees, joined at infinite distance as `forest_clusters`
+    documents.
+    Duplicate points give zero distances; a zero mutual-reachability forest edge is `forest_clusters`'
+    error (zero is no valid height), here re-raised with the number of zero entries in the k-NN table
+    (info["zero_neighbours"]). Returns the `HDBSCANResult` of `hdbscan` with one more attribute, `knn`
+    (the KNNGraph)."""
+    _native.cluster_args(min_cluster_size, method, allow_single_cluster)
+    ms = _native.mreach_args(min_cluster_size if min_samples is None else min_samples, "error")
+    _points_f32(points)
+    n = int(points.shape[0])
+    kk = max(1, ms) if k is None else k
+    kk, _, _ = _native.knn_args(kk, metric, 0)
+    if kk < max(1, ms - 1):
+        raise ValueError(f"k = {kk} is below min_samples - 1 = {ms - 1}: the core distances would not be exact")
+    if kk > n - 1:
+        raise ValueError(f"k = {kk} needs at least k + 1 points, got n = {n}"
+                         + (" (pass a smaller k or min_samples)" if k is None else ""))
+    g = knn_graph(points, kk, metric=metric)
+    try:
+        out = hdbscan(g.edges, min_cluster_size=min_cluster_size, min_samples=ms, method=method,
+                      allow_single_cluster=allow_single_cluster, short_rows="error", include_self=True)
+    except _native.GHSError as e:
+        zeros = g.knn.info["zero_neighbours"]
+        if e.code == _native.GHS_E_ARG and zeros:
+            raise _native.GHSError(e.code, f"{str(e).split(': ', 1)[-1]}; the k-NN table holds {zeros} zero distances (info['zero_neighbours']): "
+                                   "duplicate points make zero heights, which forest_clusters refuses") from e
+        raise
+    out.knn = g
+    return out
+
+
 class PathAnswers:
     """What `PathIndex.query` returns, one entry per pair, on the device.
     key: int64 holding the uint64 w << 32 | eid of the heaviest edge (largest key) on the forest path;

@@ -470,6 +470,60 @@ def hdbscan_edges(num_nodes, u, v, w, rank_weights=False, min_cluster_size=5, mi
     return (out, {"reach": h.reach.info, "cluster": c.info}) if return_info else out
 
 
+def hdbscan_points(X, min_cluster_size=5, min_samples=None, k=None, metric="euclidean", method="eom",
+                   allow_single_cluster=False, return_info=False):
+    """An (n, d) numpy array of points -> HDBSCAN end to end on the device (`device.hdbscan_points`: the
+    exact brute-force k-NN graph, core distances and mutual reachability, the solve, the dendrogram, the
+    cluster extraction), with one H2D copy. X: float32, float16 or integers with |x| < 2^24; float64 raises
+    ValueError (it is never narrowed silently: cast it yourself). Returns the dict of `hdbscan_edges`
+    without mst_raw_ids, plus core (float32, in distance units: exact, the dense definition's) and
+    mst_edges (one (a, b, distance) row per edge of the forest, float64, a < b; the forest is the
+    k-NN graph's under the mutual-reachability distance, see `device.hdbscan_points` for when that is the
+    complete graph's). k=None means max(1, min_samples). return_info=True: (dict, {"knn": ..., "reach":
+    ..., "cluster": ...})."""
+    import torch
+
+    from .device import flags_to_eids, hdbscan_points as device_hdbscan_points
+    X = np.asarray(X)
+    if X.ndim != 2:
+        raise ValueError("X: a two-dimensional (n, d) array of points expected")
+    if X.dtype == np.float64:
+        raise ValueError("X: float64 is never narrowed silently; pass X.astype(np.float32) if float32 distances "
+                         "are what you want")
+    if X.dtype not in (np.float32, np.float16) and X.dtype.kind not in "iu":
+        raise ValueError(f"X: float32 / float16 or integer points expected, got {X.dtype}")
+    if X.dtype.kind == "u":
+        if X.size and int(X.max()) >= (1 << 24):
+            raise ValueError("X: integer coordinates must satisfy |x| < 2^24 to be exact in float32")
+        X = X.astype(np.int64)
+    # ValueError (bad values) before anything touches the device
+    _native.cluster_args(min_cluster_size, method, allow_single_cluster)
+    ms = _native.mreach_args(min_cluster_size if min_samples is None else min_samples, "error")
+    kk, _, _ = _native.knn_args(max(1, ms) if k is None else k, metric, 0)
+    if kk < max(1, ms - 1):
+        raise ValueError(f"k = {kk} is below min_samples - 1 = {ms - 1}: the core distances would not be exact")
+    if kk > X.shape[0] - 1:
+        raise ValueError(f"k = {kk} needs at least k + 1 points, got n = {X.shape[0]}")
+    _native.load()
+    _native.require_gpu()
+    h = device_hdbscan_points(torch.from_numpy(np.ascontiguousarray(X)).to("cuda"), min_cluster_size=min_cluster_size,
+                              min_samples=ms, k=kk, metric=metric, method=method,
+                              allow_single_cluster=allow_single_cluster)
+    c, e = h.clusters, h.reach.edges
+    eids = flags_to_eids(h.mst.in_mst, 0, e.m)
+    mask = 0xFFFFFFFF
+    mst_edges = torch.stack([(e.u[eids].to(torch.int64) & mask).double(), (e.v[eids].to(torch.int64) & mask).double(),
+                             e.weights[eids].double()], dim=1)
+    out = {"label": c.label.cpu().numpy(), "probability": c.probability.cpu().numpy(),
+           "point_cluster": c.point_cluster.cpu().numpy().view(np.uint32), "point_lambda": c.point_lambda.cpu().numpy(),
+           "cluster_head": c.cluster_head.cpu().numpy().view(np.uint32),
+           "cluster_parent": c.cluster_parent.cpu().numpy().view(np.uint32),
+           "cluster_size": c.cluster_size.cpu().numpy().view(np.uint32), "cluster_birth": c.cluster_birth.cpu().numpy(),
+           "cluster_stability": c.cluster_stability.cpu().numpy(), "cluster_selected": c.cluster_selected.cpu().numpy(),
+           "core": h.reach.core_values().cpu().numpy(), "mst_edges": mst_edges.cpu().numpy()}
+    return (out, {"knn": h.knn.knn.info, "reach": h.reach.info, "cluster": c.info}) if return_info else out
+
+
 def fits_batch(graph):
     """True when the batch kernel takes the graph (GHS_BATCH_MAX_VERTICES / GHS_BATCH_MAX_EDGES)."""
     return graph.n <= _native.BATCH_MAX_VERTICES and graph.m <= _native.BATCH_MAX_EDGES

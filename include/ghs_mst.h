@@ -1017,6 +1017,67 @@ int ghs_mutual_reach_host(uint32_t n, uint64_t m, const uint32_t *u, const uint3
  * re-weight (read before `enable` takes effect for the next call); diagnostic */
 int ghs_mutual_reach_phases(int enable, double *ms);
 
+/* ---- k-NN graph: where does the edge list come from? (ABI 10 addition) --------------------------------
+ * The exact k nearest neighbours of every row of an (n, dim) float32 array, by brute force: the front
+ * of HDBSCAN on points. Row i of d_idx / d_dist holds the neighbours of point i.
+ * Distance. d2(a, b) is the float32 value of the chain acc = 0; for t = 0 .. dim-1 in ascending order:
+ * s = a[t] - b[t] (one rounding), acc = fmaf(s, s, acc). It is never negative, bit for bit symmetric in
+ * (a, b), 0 for equal rows, and has no cancellation: its relative error against exact arithmetic is at
+ * most (dim + 3) * 2^-23 (one rounding in s, one per fmaf, all terms >= 0, a factor 2 for the second
+ * order). The form |a|^2 + |b|^2 - 2ab has none of these properties, and the f32 MFMA that would compute
+ * it runs at the vector rate on gfx950 anyway.
+ * Metric. GHS_KNN_SQEUCLIDEAN writes d2, GHS_KNN_EUCLIDEAN the correctly rounded sqrt(d2); the selection
+ * is always on d2.
+ * Neighbours of i: the k candidates j != i with the smallest 64-bit key (float_bits(d2(i, j)) << 32) | j
+ * (non-negative floats order as their bits do). Keys are distinct, so the answer is unique: ties go to the
+ * smaller index. i is excluded by index, never by distance: a duplicate of i is an ordinary neighbour at
+ * distance 0. A row holds its neighbours in ascending key order.
+ * Determinism. The output is a pure function of (x, k, metric): the same bytes for every `slices`, every
+ * launch shape and every arrival order of candidates, and from call to call.
+ * Method (csrc/knn.hip). One workgroup owns GHS_KNN_TILE_Q queries and sweeps the candidates of its
+ * slice GHS_KNN_TILE_C at a time, both sides staged through LDS GHS_KNN_DIM_CHUNK dims at a time (tail
+ * candidates and dims padded with zeros: fmaf(0, 0, acc) == acc), 4 x 4 accumulators per lane that see
+ * the dims in ascending order. Per query a sorted list of k keys lives in LDS; a finished key that beats
+ * the list's last entry goes to the query's LDS queue and is inserted. With slices > 1 every slice
+ * writes its lists to the workspace and a merge kernel takes the k smallest. slices == 0: chosen from n
+ * alone (a fixed target of workgroups, clamped to [1, GHS_KNN_MAX_SLICES]). Everything runs on `stream`;
+ * one host sync per call. Workspace (ghs_knn_workspace_bytes): 256 B of status, and 8 B * slices * n * k
+ * of keys when slices > 1.
+ * Errors, checked before any device work (so GHS_E_ARG, not GHS_E_NODEVICE, on a host without GPU): a
+ * NULL result; k == 0, k > GHS_KNN_MAX_K; dim == 0, dim > GHS_KNN_MAX_DIM; an unknown metric; slices >
+ * GHS_KNN_MAX_SLICES; then, for n >= 1: k > n - 1; n * k >= 2^32; NULL pointers; misaligned pointers
+ * (16 bytes for d_x and the workspace, 4 for d_idx / d_dist; the rows of d_x are only 4-byte aligned when
+ * dim % 4 != 0); overlapping pointers: GHS_E_ARG; workspace_bytes short: GHS_E_NOMEM. n == 0: GHS_OK, no
+ * device work, the pointers may be NULL. After the sync: a NaN or +-inf coordinate gives GHS_E_ARG
+ * ("non-finite coordinate"); the outputs are then unspecified, nothing was read or written out of bounds
+ * and no key was formed from a NaN. A d2 that overflows to +inf for finite coordinates is an ordinary
+ * value. */
+#define GHS_KNN_MAX_K      128u
+#define GHS_KNN_MAX_DIM    4096u
+#define GHS_KNN_MAX_SLICES 64u
+#define GHS_KNN_SQEUCLIDEAN 0u
+#define GHS_KNN_EUCLIDEAN   1u
+#define GHS_KNN_TILE_Q     64u    /* queries of one workgroup */
+#define GHS_KNN_TILE_C     64u    /* candidates of one sweep step */
+#define GHS_KNN_DIM_CHUNK  32u    /* dims staged through LDS at a time */
+typedef struct ghs_knn_result {   /* 48 bytes */
+  uint64_t pairs;            /* ordered pairs evaluated: n * (n - 1) */
+  uint64_t zero_neighbours;  /* entries of d_dist equal to 0: duplicate points among the neighbours */
+  uint32_t slices;           /* candidate slices the scan ran with */
+  uint32_t query_tiles;
+  double   ms_total;         /* host wall time of the call */
+  uint64_t reserved[2];      /* 0 */
+} ghs_knn_result_t;
+size_t ghs_knn_workspace_bytes(uint32_t n, uint32_t dim, uint32_t k, uint32_t slices);   /* host only, no GPU needed */
+int ghs_knn_device(uint32_t n, uint32_t dim, const float *d_x /* n*dim, row-major */, uint32_t k,
+                   uint32_t metric, uint32_t slices /* 0 = auto */,
+                   uint32_t *d_idx /* n*k */, float *d_dist /* n*k */,
+                   void *d_workspace, size_t workspace_bytes, void *stream, ghs_knn_result_t *result);
+/* the same for host arrays (copy in, run, copy out on the default stream, slices = auto); the argument
+ * errors above except the alignments and the workspace, then GHS_E_NODEVICE without a GPU */
+int ghs_knn_host(uint32_t n, uint32_t dim, const float *x, uint32_t k, uint32_t metric,
+                 uint32_t *idx, float *dist, ghs_knn_result_t *result);
+
 /* device-side canonicity check: *ok = 1 iff u < v < n and (u, v) strictly ascending */
 int ghs_check_canonical(uint32_t n, uint64_t m, const uint32_t *d_u, const uint32_t *d_v, void *stream, int *ok);
 
