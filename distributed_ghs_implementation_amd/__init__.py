@@ -37,6 +37,9 @@ DeviceEdges.hdbscan, mst.hdbscan_edges, CLI --mutual-reachability OUT.npz, --hdb
 where the graph comes from (the exact brute-force k nearest neighbours of float32 points, the symmetrised
 k-NN graph as a canonical list, HDBSCAN from points end to end): device.knn, device.knn_graph,
 device.hdbscan_points, mst.hdbscan_points, CLI --points X.npy --knn K --knn-graph OUT.npz / --hdbscan OUT.npz;
+the exact MST of the complete graph on points (Euclidean or mutual-reachability) and HDBSCAN exact from
+points to labels: device.emst, device.hdbscan_points(exact=True), mst.emst_points,
+mst.hdbscan_points(exact=True), CLI --points X.npy --emst OUT.npz / --hdbscan OUT.npz --exact;
 multi-GPU: distributed.DistributedMST. Float, negative and 64-bit
 weights: rank-mapped by graph.canonicalize on the host, or on the device with rank_weights=True
 (minimum_spanning_forest_edges, DeviceEdges.from_raw, canonicalize_device; device.weight_ranks).

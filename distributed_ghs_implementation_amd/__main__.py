@@ -160,7 +160,8 @@ def run_batch_dir(args):
 
 
 def run_points(args):
-    """--points X.npy: the k-NN graph (--knn-graph) and / or HDBSCAN from points (--hdbscan)."""
+    """--points X.npy: the k-NN graph (--knn-graph), the exact MST (--emst) and / or HDBSCAN from points
+    (--hdbscan, with --exact on the exact MST)."""
     import numpy as np
 
     t0 = time.perf_counter()
@@ -184,16 +185,27 @@ def run_points(args):
                   f"zero distances: {g.knn.info['zero_neighbours']}  knn: {g.knn.info['ms_total']:.3f} ms  "
                   f"read: {t_read * 1e3:.1f} ms")
             print(f"k-NN graph saved to: {args.knn_graph}")
+    if args.emst is not None:
+        from .mst import emst_points
+        out, info = emst_points(X, min_samples=args.min_samples, metric=metric, return_info=True)
+        np.savez(args.emst, **{k: v for k, v in out.items() if v is not None})
+        if not args.quiet:
+            what = "Euclidean" if args.min_samples is None else f"mutual-reachability (min_samples = {args.min_samples})"
+            print(f"Points: {X.shape[0]} x {X.shape[1]}  exact {what} MST: {info['num_edges']} edges  "
+                  f"rounds: {info['rounds']}  zero edges: {info['zero_edges']}  emst: {info['ms_total']:.3f} ms  "
+                  f"read: {t_read * 1e3:.1f} ms")
+            print(f"Exact MST saved to: {args.emst}")
     if args.hdbscan is not None:
         from .mst import hdbscan_points
         mcs = 5 if args.min_cluster_size is None else args.min_cluster_size
         out, info = hdbscan_points(X, min_cluster_size=mcs, min_samples=args.min_samples, k=args.knn, metric=metric,
                                    method=args.cluster_method, allow_single_cluster=args.allow_single_cluster,
-                                   return_info=True)
+                                   return_info=True, exact=args.exact)
         np.savez(args.hdbscan, **out)
         if not args.quiet:
+            how = f"exact MST, {info['emst']['rounds']} rounds" if args.exact else f"k = {info['knn']['k']}"
             print(f"HDBSCAN from points: {info['cluster']['num_selected']} clusters, {info['cluster']['num_noise']} noise "
-                  f"points of {X.shape[0]} (k = {info['knn']['k']}, {metric})")
+                  f"points of {X.shape[0]} ({how}, {metric})")
             print(f"HDBSCAN saved to: {args.hdbscan}")
     return 0
 
@@ -257,13 +269,19 @@ def main(argv=None):
     ap.add_argument("--hops", action="store_true", help="with --distances / --diameters: count edges, not weights")
     ap.add_argument("--points", type=str, default=None, metavar="X.npy",
                     help="an (n, d) array of points instead of a graph (float32 / float16 / integers): the exact k-NN "
-                         "graph is built on the device; takes --knn, --metric, --knn-graph and --hdbscan")
+                         "graph is built on the device; takes --knn, --metric, --knn-graph, --emst, --hdbscan and --exact")
     ap.add_argument("--knn", type=int, default=None, metavar="K",
                     help="with --points: neighbours per point (default with --hdbscan: --min-samples)")
     ap.add_argument("--metric", choices=["euclidean", "sqeuclidean"], default=None,
                     help="with --points: the distance written and clustered on (default euclidean)")
     ap.add_argument("--knn-graph", type=str, default=None, metavar="OUT.npz",
                     help="with --points: write the k-NN table (idx, dist) and the symmetrised canonical graph (u, v, w)")
+    ap.add_argument("--emst", type=str, default=None, metavar="OUT.npz",
+                    help="with --points: write the exact minimum spanning tree of the complete graph on the points "
+                         "(u, v, w): Euclidean, or with --min-samples K the mutual-reachability tree (and core)")
+    ap.add_argument("--exact", action="store_true",
+                    help="with --points --hdbscan: cluster on the exact mutual-reachability MST, not the k-NN graph's "
+                         "forest (--knn is ignored)")
     ap.add_argument("--gpus", type=int, default=1, help="GPUs driven by this one process (RCCL clique)")
     ap.add_argument("--generator", choices=["rmat", "grid"], default=None, help="synthetic graph instead of a file")
     ap.add_argument("--scale", type=int, default=16, help="R-MAT scale (2^scale vertices) / grid side k")
@@ -281,8 +299,8 @@ def main(argv=None):
         ap.error("--min-cluster-size needs --clusters OUT.npz")
     if args.hdbscan is not None and args.min_cluster_size is not None and args.min_cluster_size < 2:
         ap.error("--hdbscan OUT.npz takes --min-cluster-size K with K >= 2")
-    if args.min_samples is not None and args.hdbscan is None and args.mutual_reachability is None:
-        ap.error("--min-samples needs --hdbscan OUT.npz or --mutual-reachability OUT.npz")
+    if args.min_samples is not None and args.hdbscan is None and args.mutual_reachability is None and args.emst is None:
+        ap.error("--min-samples needs --hdbscan OUT.npz or --mutual-reachability OUT.npz (or --points X.npy --emst OUT.npz)")
     if args.min_samples is not None and args.min_samples < 1:
         ap.error("--min-samples K needs K >= 1")
     if args.clusters is not None and args.max_weight is not None:
@@ -296,11 +314,15 @@ def main(argv=None):
         ap.error("--distances OUT.npz needs --pairs PAIRS.npy")
     if args.points is None and (args.knn is not None or args.metric is not None or args.knn_graph is not None):
         ap.error("--knn / --metric / --knn-graph need --points X.npy")
+    if args.points is None and (args.emst is not None or args.exact):
+        ap.error("--emst / --exact need --points X.npy")
     if args.points is not None:
         if args.graph is not None or args.generator is not None or args.batch_dir is not None:
             ap.error("--points excludes --graph, --generator and --batch-dir")
-        if args.knn_graph is None and args.hdbscan is None:
-            ap.error("--points X.npy needs --knn-graph OUT.npz or --hdbscan OUT.npz")
+        if args.knn_graph is None and args.hdbscan is None and args.emst is None:
+            ap.error("--points X.npy needs --knn-graph OUT.npz or --hdbscan OUT.npz or --emst OUT.npz")
+        if args.exact and args.hdbscan is None:
+            ap.error("--exact needs --hdbscan OUT.npz")
         if args.knn is not None and not 1 <= args.knn <= 128:
             ap.error("--knn K needs 1 <= K <= 128")
         if args.knn_graph is not None and args.knn is None:
@@ -308,7 +330,8 @@ def main(argv=None):
         others = ("labels", "cluster_out", "clusters", "mutual_reachability", "rooted", "dendrogram", "paths",
                   "replacements", "distances", "diameters", "stretch", "check_result")
         if any(getattr(args, o) is not None for o in others) or args.check or args.check_device:
-            ap.error("--points takes --knn-graph OUT.npz and --hdbscan OUT.npz only (the graph outputs need a graph)")
+            ap.error("--points takes --knn-graph OUT.npz and --hdbscan OUT.npz only, and --emst OUT.npz (the graph outputs "
+                     "need a graph)")
         return run_points(args)
     if args.batch_dir is not None:
         return run_batch_dir(args)

@@ -77,6 +77,7 @@ EXPORTED_SYMBOLS = (
     "ghs_forest_cluster_host",
     "ghs_mutual_reach_workspace_bytes", "ghs_mutual_reach_device", "ghs_mutual_reach_host", "ghs_mutual_reach_phases",
     "ghs_knn_workspace_bytes", "ghs_knn_device", "ghs_knn_host",
+    "ghs_emst_workspace_bytes", "ghs_emst_device", "ghs_emst_host", "ghs_emst_rounds",
 )
 
 
@@ -372,6 +373,43 @@ def knn_args(k, metric, slices=0, n=None, dim=None):
         if int(n) * kk >= (1 << 32):
             raise ValueError("n * k must be < 2^32")
     return kk, KNN_METRICS[metric], ss
+
+
+class EmstResult(ctypes.Structure):
+    """ghs_emst_result_t: what ghs_emst_device / ghs_emst_host found."""
+    _fields_ = [
+        ("num_edges", ctypes.c_uint64),
+        ("pairs", ctypes.c_uint64),
+        ("zero_edges", ctypes.c_uint64),
+        ("rounds", ctypes.c_uint32),
+        ("slices", ctypes.c_uint32),
+        ("query_tiles", ctypes.c_uint32),
+        ("reserved0", ctypes.c_uint32),
+        ("components_after_first_round", ctypes.c_uint64),
+        ("ms_total", ctypes.c_double),
+        ("reserved", ctypes.c_uint64 * 1),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
+
+
+def emst_args(metric, slices=0, n=None, dim=None):
+    """(metric code, slices) of the exact-MST entry points; ValueError for what they would refuse, before
+    anything touches the device. n, dim: the points' shape when it is known."""
+    if metric not in KNN_METRICS:
+        raise ValueError(f"metric: 'euclidean' or 'sqeuclidean' expected, got {metric!r}")
+    try:
+        ss = int(slices)
+    except (TypeError, ValueError):
+        raise ValueError(f"slices must be an integer in [0, {GHS_KNN_MAX_SLICES}] (0: chosen from n), got {slices!r}") from None
+    if ss != slices or not 0 <= ss <= GHS_KNN_MAX_SLICES:
+        raise ValueError(f"slices must be an integer in [0, {GHS_KNN_MAX_SLICES}] (0: chosen from n), got {slices!r}")
+    if dim is not None and not 1 <= int(dim) <= GHS_KNN_MAX_DIM:
+        raise ValueError(f"points must have between 1 and {GHS_KNN_MAX_DIM} columns, got {dim}")
+    if n is not None and int(n) - 1 >= (1 << 31):
+        raise ValueError("at most 2^31 points (n - 1 tree edges must be < 2^31)")
+    return KNN_METRICS[metric], ss
 
 
 class PathsResult(ctypes.Structure):
@@ -726,6 +764,10 @@ def load():
             "ghs_knn_workspace_bytes": (sz, [u32, u32, u32, u32]),
             "ghs_knn_device": (i32, [u32, u32, vp, u32, u32, u32, vp, vp, vp, sz, vp, P(KnnResult)]),
             "ghs_knn_host": (i32, [u32, u32, vp, u32, u32, vp, vp, P(KnnResult)]),
+            "ghs_emst_workspace_bytes": (sz, [u32, u32, u32]),
+            "ghs_emst_device": (i32, [u32, u32, vp, vp, u32, u32, vp, vp, vp, vp, sz, vp, P(EmstResult)]),
+            "ghs_emst_host": (i32, [u32, u32, vp, vp, u32, vp, vp, vp, P(EmstResult)]),
+            "ghs_emst_rounds": (i32, [i32, u32, P(u32), P(ctypes.c_double), P(u32)]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(L, name)

@@ -1135,8 +1135,118 @@ def knn_graph(points, k, metric="euclidean"):
     return KNNGraph(edges, nn)
 
 
+class EMST:
+    """What `emst` found: the n - 1 edges of the exact minimum spanning tree of the complete graph on the
+    points, a canonical edge list. u, v: int32 GPU tensors of uint32 bits, u[e] < v[e], (u, v) strictly
+    ascending; w: float32, the weights (squared for metric="sqeuclidean"); info: the fields of
+    ghs_emst_result_t as a dict, plus n and metric."""
+
+    def __init__(self, n, u, v, w, info=None):
+        self.n, self.u, self.v, self.w, self.info = int(n), u, v, w, info
+        self._edges = None
+
+    def edges(self):
+        """The tree as `DeviceEdges` (through `canonicalize_device(..., rank_weights=True)`): `w` the ranks
+        of the weights, `weights` the float32 weights. The list is canonical already, so `src` is the
+        identity."""
+        if self._edges is None:
+            self._edges = canonicalize_device(self.n, self.u, self.v, self.w, rank_weights=True)
+        return self._edges
+
+
+def emst(points, core2=None, metric="euclidean", slices=0):
+    """The exact minimum spanning tree of the complete graph on the rows of `points`, on the device
+    (ghs_emst_device, csrc/emst.hip): the Euclidean MST, or with `core2` (n float32 SQUARED core distances,
+    finite and >= 0, on the points' device) the mutual-reachability MST HDBSCAN is defined on. points: as
+    `knn` takes them (float32 as it is, float16 / bfloat16 / small integers widened exactly, float64
+    refused). The weight of {i, j} is max(d2(i, j), core2[i], core2[j]) with d2 the float32 chain of `knn`;
+    pairs are ordered by (weight bits, min, max), so the tree is unique: canonical Kruskal's over all
+    n (n - 1) / 2 pairs. The same bytes on every call and for every `slices` (0: chosen from n; a tuning
+    knob only). Boruvka rounds, each one brute-force sweep: O(n^2 d log n) work, no k. Runs on torch's
+    current stream; a NaN or infinite coordinate, or a core2 that is NaN, infinite or negative, raises
+    GHSError (GHS_E_ARG). Returns an `EMST` (u, v, w, info, edges())."""
+    points = _points_f32(points)
+    n, dim = int(points.shape[0]), int(points.shape[1])
+    mcode, ss = _native.emst_args(metric, slices, n=n, dim=dim)
+    if core2 is not None:
+        if not (isinstance(core2, torch.Tensor) and core2.dim() == 1 and core2.dtype == torch.float32):
+            raise ValueError("core2: a one-dimensional float32 GPU tensor of squared core distances expected")
+        if int(core2.numel()) != n:
+            raise ValueError(f"core2: {n} entries expected (one per point), got {int(core2.numel())}")
+    L = _native.load()
+    _native.require_gpu()
+    if not points.is_cuda:
+        raise ValueError("points: a two-dimensional (n, d) GPU tensor expected")
+    if core2 is not None and core2.device != points.device:
+        raise ValueError("core2 must be on the points' device")
+    dev = points.device
+    t = max(n - 1, 0)
+    with torch.cuda.device(dev):
+        if points.dtype in (torch.int32, torch.int64) and points.numel():  # the narrower ones cannot reach 2^24
+            if bool(((points >= (1 << 24)) | (points <= -(1 << 24))).any()):
+                raise ValueError("points: integer coordinates must satisfy |x| < 2^24 to be exact in float32")
+        x = points.to(torch.float32).contiguous()
+        if x.data_ptr() % 16:
+            x = x.clone()  # a view that starts off a 16-byte boundary
+        c2 = core2.contiguous() if core2 is not None else None
+        u = torch.empty(t, dtype=torch.int32, device=dev)
+        v = torch.empty(t, dtype=torch.int32, device=dev)
+        w = torch.empty(t, dtype=torch.float32, device=dev)
+        res = _native.EmstResult()
+        ws_bytes = int(L.ghs_emst_workspace_bytes(n, dim, ss))
+        ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=dev)
+        _native.check(L.ghs_emst_device(n, dim, _ptr(x), _ptr(c2) if c2 is not None else None, mcode, ss, _ptr(u), _ptr(v),
+                                        _ptr(w), _ptr(ws), ws_bytes, _stream(), ctypes.byref(res)))
+        del ws
+    info = res.as_dict()
+    info["n"], info["metric"] = n, metric
+    return EMST(n, u, v, w, info)
+
+
+def _rounded_sqrt(t):
+    """the correctly rounded float32 square root of a small GPU vector, as the kernels' sqrtf gives it (numpy's is
+    IEEE's; n values through the host, next to n^2 work on the device)"""
+    import numpy as np
+    return torch.from_numpy(np.sqrt(t.cpu().numpy())).to(t.device)
+
+
+def _hdbscan_points_exact(points, min_cluster_size, ms, metric, method, allow_single_cluster):
+    """hdbscan_points(exact=True): the cores from the k-NN table, the exact mutual-reachability MST, then
+    the dendrogram and the clusters of that tree."""
+    n = int(points.shape[0])
+    if n < 2:
+        raise ValueError(f"exact=True needs at least 2 points, got n = {n}")
+    _native.emst_args(metric, 0, n=n, dim=int(points.shape[1]))
+    if ms >= 2:
+        nn = knn(points, ms - 1, metric="sqeuclidean")   # include_self=True: the point is its own first neighbour
+        core2 = nn.dist[:, ms - 2].contiguous()
+    else:
+        core2 = torch.zeros(n, dtype=torch.float32, device=points.device)
+    tree = emst(points, core2=core2, metric=metric)
+    edges = tree.edges()
+    mst = DeviceMST(edges)
+    res, _ = mst.run()
+    flagged = int(mst.in_mst[: edges.m].sum()) if edges.m else 0
+    if edges.m != n - 1 or res.num_mst_edges != n - 1 or flagged != n - 1:
+        raise _native.GHSError(_native.GHS_E_STATE, f"the exact MST's {edges.m} edges are no spanning tree of {n} points: "
+                               f"the solve flagged {flagged}")
+    dg = mst.dendrogram()
+    try:
+        cl = dg.clusters(edges, min_cluster_size=min_cluster_size, method=method, allow_single_cluster=allow_single_cluster)
+    except _native.GHSError as e:
+        zeros = tree.info["zero_edges"]
+        if e.code == _native.GHS_E_ARG and zeros:
+            raise _native.GHSError(e.code, f"{str(e).split(': ', 1)[-1]}; the exact MST holds {zeros} edges of weight zero "
+                                   "(info['zero_edges']): duplicate points make zero heights, which forest_clusters refuses") from e
+        raise
+    out = HDBSCANResult(None, mst, dg, cl)
+    out.emst = tree
+    out.core = _rounded_sqrt(core2) if metric == "euclidean" else core2
+    return out
+
+
 def hdbscan_points(points, min_cluster_size=5, min_samples=None, k=None, metric="euclidean", method="eom",
-                   allow_single_cluster=False):
+                   allow_single_cluster=False, exact=False):
     """HDBSCAN of points end to end on the device: `knn_graph(points, k)` -> `hdbscan(edges, ...,
     include_self=True, short_rows="error")`. include_self=True is scikit-learn's convention for points (a
     point is its own first neighbour), min_samples=None means min_cluster_size, k=None means
@@ -1153,11 +1263,23 @@ def hdbscan_points(points, min_cluster_size=5, min_samples=None, k=None, metric=
     Duplicate points give zero distances; a zero mutual-reachability forest edge is `forest_clusters`'
     error (zero is no valid height), here re-raised with the number of zero entries in the k-NN table
     (info["zero_neighbours"]). Returns the `HDBSCANResult` of `hdbscan` with one more attribute, `knn`
-    (the KNNGraph)."""
+    (the KNNGraph).
+    exact=True takes the exact path instead, and the forest is exact too: the cores come from
+    `knn(points, max(1, min_samples - 1), metric="sqeuclidean")` (column min_samples - 2; zero for
+    min_samples == 1: the same include_self=True convention), then `emst(points, core2=...)` gives THE minimum
+    spanning tree of the complete mutual-reachability graph, `DeviceMST(tree.edges()).run()` flags every
+    edge of it (anything else raises), then `dendrogram()` and `clusters()`. `k` is ignored: nothing depends
+    on it. The result has reach=None and two more attributes: `emst` (the EMST) and `core` (float32, in the
+    metric's units). A zero-weight tree edge is `forest_clusters`' error, re-raised with the tree's number of
+    zero edges (info["zero_edges"]). Cost: O(n^2 d log n) instead of O(n^2 d)."""
     _native.cluster_args(min_cluster_size, method, allow_single_cluster)
     ms = _native.mreach_args(min_cluster_size if min_samples is None else min_samples, "error")
     _points_f32(points)
     n = int(points.shape[0])
+    if exact:
+        if metric not in _native.KNN_METRICS:
+            raise ValueError(f"metric: 'euclidean' or 'sqeuclidean' expected, got {metric!r}")
+        return _hdbscan_points_exact(points, min_cluster_size, ms, metric, method, allow_single_cluster)
     kk = max(1, ms) if k is None else k
     kk, _, _ = _native.knn_args(kk, metric, 0)
     if kk < max(1, ms - 1):

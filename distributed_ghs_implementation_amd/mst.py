@@ -470,20 +470,8 @@ def hdbscan_edges(num_nodes, u, v, w, rank_weights=False, min_cluster_size=5, mi
     return (out, {"reach": h.reach.info, "cluster": c.info}) if return_info else out
 
 
-def hdbscan_points(X, min_cluster_size=5, min_samples=None, k=None, metric="euclidean", method="eom",
-                   allow_single_cluster=False, return_info=False):
-    """An (n, d) numpy array of points -> HDBSCAN end to end on the device (`device.hdbscan_points`: the
-    exact brute-force k-NN graph, core distances and mutual reachability, the solve, the dendrogram, the
-    cluster extraction), with one H2D copy. X: float32, float16 or integers with |x| < 2^24; float64 raises
-    ValueError (it is never narrowed silently: cast it yourself). Returns the dict of `hdbscan_edges`
-    without mst_raw_ids, plus core (float32, in distance units: exact, the dense definition's) and
-    mst_edges (one (a, b, distance) row per edge of the forest, float64, a < b; the forest is the
-    k-NN graph's under the mutual-reachability distance, see `device.hdbscan_points` for when that is the
-    complete graph's). k=None means max(1, min_samples). return_info=True: (dict, {"knn": ..., "reach":
-    ..., "cluster": ...})."""
-    import torch
-
-    from .device import flags_to_eids, hdbscan_points as device_hdbscan_points
+def _points_array(X):
+    """X as the numpy array the device layer takes; ValueError for what it would refuse."""
     X = np.asarray(X)
     if X.ndim != 2:
         raise ValueError("X: a two-dimensional (n, d) array of points expected")
@@ -496,9 +484,81 @@ def hdbscan_points(X, min_cluster_size=5, min_samples=None, k=None, metric="eucl
         if X.size and int(X.max()) >= (1 << 24):
             raise ValueError("X: integer coordinates must satisfy |x| < 2^24 to be exact in float32")
         X = X.astype(np.int64)
+    return X
+
+
+def emst_points(X, min_samples=None, metric="euclidean", return_info=False):
+    """An (n, d) numpy array of points -> the exact minimum spanning tree of the complete graph on them, on
+    the device (`device.emst`). min_samples=None: the Euclidean MST (single linkage on points). min_samples
+    = K >= 1: the mutual-reachability MST of HDBSCAN, with the core distance of a point the distance to its
+    (K - 1)-th nearest other point (scikit-learn's convention: the point counts as its own first neighbour).
+    X as `hdbscan_points` takes it. Returns {"u", "v": uint32, "w": float32 (squared for
+    metric="sqeuclidean"), "core": float32 in the metric's units or None}; the n - 1 edges are canonical
+    (u < v, ascending). return_info=True: (dict, the fields of ghs_emst_result_t)."""
+    import torch
+
+    from .device import emst, knn
+    X = _points_array(X)
+    n = X.shape[0]
+    _native.emst_args(metric, 0, n=n, dim=X.shape[1])
+    ms = None if min_samples is None else _native.mreach_args(min_samples, "error")
+    if ms is not None and ms >= 2:
+        _native.knn_args(ms - 1, "sqeuclidean", 0, n=n, dim=X.shape[1])
+    _native.load()
+    _native.require_gpu()
+    pts = torch.from_numpy(np.ascontiguousarray(X)).to("cuda")
+    core2 = None
+    if ms is not None:
+        core2 = (knn(pts, ms - 1, metric="sqeuclidean").dist[:, ms - 2].contiguous() if ms >= 2
+                 else torch.zeros(n, dtype=torch.float32, device=pts.device))
+    t = emst(pts, core2=core2, metric=metric)
+    core = None if core2 is None else core2.cpu().numpy()
+    if core is not None and metric == "euclidean":
+        core = np.sqrt(core)      # float32, correctly rounded
+    out = {"u": t.u.cpu().numpy().view(np.uint32), "v": t.v.cpu().numpy().view(np.uint32), "w": t.w.cpu().numpy(),
+           "core": core}
+    return (out, t.info) if return_info else out
+
+
+def hdbscan_points(X, min_cluster_size=5, min_samples=None, k=None, metric="euclidean", method="eom",
+                   allow_single_cluster=False, return_info=False, exact=False):
+    """An (n, d) numpy array of points -> HDBSCAN end to end on the device (`device.hdbscan_points`: the
+    exact brute-force k-NN graph, core distances and mutual reachability, the solve, the dendrogram, the
+    cluster extraction), with one H2D copy. X: float32, float16 or integers with |x| < 2^24; float64 raises
+    ValueError (it is never narrowed silently: cast it yourself). Returns the dict of `hdbscan_edges`
+    without mst_raw_ids, plus core (float32, in distance units: exact, the dense definition's) and
+    mst_edges (one (a, b, distance) row per edge of the forest, float64, a < b; the forest is the
+    k-NN graph's under the mutual-reachability distance, see `device.hdbscan_points` for when that is the
+    complete graph's). k=None means max(1, min_samples). return_info=True: (dict, {"knn": ..., "reach":
+    ..., "cluster": ...}).
+    exact=True: the forest is the exact minimum spanning tree of the complete mutual-reachability graph
+    (`device.hdbscan_points(..., exact=True)`; k is ignored), mst_edges its n - 1 edges, and the info dict is
+    {"emst": ..., "cluster": ...}."""
+    import torch
+
+    from .device import flags_to_eids, hdbscan_points as device_hdbscan_points
+    X = _points_array(X)
     # ValueError (bad values) before anything touches the device
     _native.cluster_args(min_cluster_size, method, allow_single_cluster)
     ms = _native.mreach_args(min_cluster_size if min_samples is None else min_samples, "error")
+    if exact:
+        _native.emst_args(metric, 0, n=X.shape[0], dim=X.shape[1])
+        if X.shape[0] < 2:
+            raise ValueError(f"exact=True needs at least 2 points, got n = {X.shape[0]}")
+        if ms >= 2:
+            _native.knn_args(ms - 1, "sqeuclidean", 0, n=X.shape[0], dim=X.shape[1])
+        _native.load()
+        _native.require_gpu()
+        h = device_hdbscan_points(torch.from_numpy(np.ascontiguousarray(X)).to("cuda"), min_cluster_size=min_cluster_size,
+                                  min_samples=ms, metric=metric, method=method, allow_single_cluster=allow_single_cluster,
+                                  exact=True)
+        c, t = h.clusters, h.emst
+        mask = 0xFFFFFFFF
+        mst_edges = torch.stack([(t.u.to(torch.int64) & mask).double(), (t.v.to(torch.int64) & mask).double(), t.w.double()],
+                                dim=1)
+        out = _clusters_dict(c)
+        out["core"], out["mst_edges"] = h.core.cpu().numpy(), mst_edges.cpu().numpy()
+        return (out, {"emst": t.info, "cluster": c.info}) if return_info else out
     kk, _, _ = _native.knn_args(max(1, ms) if k is None else k, metric, 0)
     if kk < max(1, ms - 1):
         raise ValueError(f"k = {kk} is below min_samples - 1 = {ms - 1}: the core distances would not be exact")
@@ -514,14 +574,19 @@ def hdbscan_points(X, min_cluster_size=5, min_samples=None, k=None, metric="eucl
     mask = 0xFFFFFFFF
     mst_edges = torch.stack([(e.u[eids].to(torch.int64) & mask).double(), (e.v[eids].to(torch.int64) & mask).double(),
                              e.weights[eids].double()], dim=1)
-    out = {"label": c.label.cpu().numpy(), "probability": c.probability.cpu().numpy(),
-           "point_cluster": c.point_cluster.cpu().numpy().view(np.uint32), "point_lambda": c.point_lambda.cpu().numpy(),
-           "cluster_head": c.cluster_head.cpu().numpy().view(np.uint32),
-           "cluster_parent": c.cluster_parent.cpu().numpy().view(np.uint32),
-           "cluster_size": c.cluster_size.cpu().numpy().view(np.uint32), "cluster_birth": c.cluster_birth.cpu().numpy(),
-           "cluster_stability": c.cluster_stability.cpu().numpy(), "cluster_selected": c.cluster_selected.cpu().numpy(),
-           "core": h.reach.core_values().cpu().numpy(), "mst_edges": mst_edges.cpu().numpy()}
+    out = _clusters_dict(c)
+    out["core"], out["mst_edges"] = h.reach.core_values().cpu().numpy(), mst_edges.cpu().numpy()
     return (out, {"knn": h.knn.knn.info, "reach": h.reach.info, "cluster": c.info}) if return_info else out
+
+
+def _clusters_dict(c):
+    """a device.Clusters as the numpy arrays hdbscan_points returns"""
+    return {"label": c.label.cpu().numpy(), "probability": c.probability.cpu().numpy(),
+            "point_cluster": c.point_cluster.cpu().numpy().view(np.uint32), "point_lambda": c.point_lambda.cpu().numpy(),
+            "cluster_head": c.cluster_head.cpu().numpy().view(np.uint32),
+            "cluster_parent": c.cluster_parent.cpu().numpy().view(np.uint32),
+            "cluster_size": c.cluster_size.cpu().numpy().view(np.uint32), "cluster_birth": c.cluster_birth.cpu().numpy(),
+            "cluster_stability": c.cluster_stability.cpu().numpy(), "cluster_selected": c.cluster_selected.cpu().numpy()}
 
 
 def fits_batch(graph):

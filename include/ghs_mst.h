@@ -1081,6 +1081,70 @@ int ghs_knn_host(uint32_t n, uint32_t dim, const float *x, uint32_t k, uint32_t 
 /* device-side canonicity check: *ok = 1 iff u < v < n and (u, v) strictly ascending */
 int ghs_check_canonical(uint32_t n, uint64_t m, const uint32_t *d_u, const uint32_t *d_v, void *stream, int *ok);
 
+/* ---- exact MST from points: the tree the k-NN forest only approximates (ABI 10 addition) -----------------
+ * The minimum spanning tree of the complete graph on the rows of an (n, dim) float32 array, exactly: the
+ * Euclidean MST (single linkage on points), or with core distances the mutual-reachability MST that HDBSCAN
+ * is defined on. No k, no forest: one tree of n - 1 edges.
+ * Inputs. d_x: (n, dim) float32, row-major. d_core2: NULL, or n float32 SQUARED core distances, every value
+ * finite and >= 0; NULL means all zero.
+ * Weight. w2(i, j) = max(d2(i, j), core2[i], core2[j]) for the unordered pair {i, j}. d2 is bit for bit the
+ * chain of ghs_knn_device: acc = 0; for t = 0 .. dim-1 in ascending order: s = a[t] - b[t] (one rounding),
+ * acc = fmaf(s, s, acc). The max is taken on float32 values, so it is exact. A d2 that overflows to +inf for
+ * finite coordinates is an ordinary value.
+ * Order. The key of the pair (u, v), u < v, is the triple (float_bits(w2), u, v), compared
+ * lexicographically: the (w, eid) key of this library on the canonical list of all n (n - 1) / 2 pairs.
+ * Keys are distinct, so the MST is unique: the tree canonical Kruskal builds over all pairs in that order.
+ * Output. The n - 1 tree edges as a canonical edge list: d_u[e] < d_v[e], (u, v) strictly ascending.
+ * d_w[e] is float32: w2 for GHS_KNN_SQEUCLIDEAN, the correctly rounded sqrt(w2) for GHS_KNN_EUCLIDEAN.
+ * Determinism. The output is a pure function of (x, core2, metric): the same bytes for every `slices`,
+ * every launch shape and from call to call.
+ * Method (csrc/emst.hip). Boruvka rounds, at most ceil(log2 n) of them (GHS_E_ROUNDCAP guards the loop). In
+ * a round one brute-force sweep (the tile shape of ghs_knn_device: GHS_KNN_TILE_Q queries x GHS_KNN_TILE_C
+ * candidates, GHS_KNN_DIM_CHUNK dims at a time) finds for every point i the smallest (float_bits(w2) << 32
+ * | j) over the points j of another component, kept in registers and combined by one 64-bit atomicMin per
+ * query and slice: for a fixed i that is also i's smallest pair key, because among equal weights any j < i
+ * beats every j > i and a smaller j beats a larger one. Two passes over the points reduce them to each
+ * component's smallest 96-bit key; a component hooks to the component of its edge's far end (of a mutual
+ * pair the smaller label stays root and only it emits the edge), pointer jumping makes stars. One host sync
+ * per round brings back the edge count. A pairs sort by u << 32 | v fixes the byte order, a last pass writes
+ * d_w. Integer atomics only. `slices`: 0 = chosen from n alone, as ghs_knn_device does.
+ * Workspace (ghs_emst_workspace_bytes): 256 B of status, 28 B per point, 24 B per edge, the sort's scratch.
+ * Errors, checked before any device work (so GHS_E_ARG, not GHS_E_NODEVICE, on a host without GPU): a NULL
+ * result; dim == 0, dim > GHS_KNN_MAX_DIM; an unknown metric; slices > GHS_KNN_MAX_SLICES; then n == 0:
+ * GHS_OK, no device work, the pointers may be NULL; n == 1: GHS_OK, zero edges, d_u / d_v / d_w may be NULL;
+ * then n - 1 >= 2^31; NULL pointers (d_core2 may be NULL); misaligned pointers (16 bytes for d_x and the
+ * workspace, 4 for the rest); overlapping pointers: GHS_E_ARG; workspace_bytes short: GHS_E_NOMEM. Checked on
+ * the device before any key is formed: a NaN or +-inf coordinate gives GHS_E_ARG ("non-finite coordinate"),
+ * a core2 that is NaN, infinite or negative GHS_E_ARG ("bad core distance"); the outputs are then
+ * unspecified and nothing was read or written out of bounds. */
+typedef struct ghs_emst_result {   /* 64 bytes */
+  uint64_t num_edges;        /* n - 1 */
+  uint64_t pairs;            /* ordered pairs evaluated, summed over rounds: rounds * n * (n - 1) */
+  uint64_t zero_edges;       /* tree edges of weight 0: duplicate points */
+  uint32_t rounds;           /* Boruvka rounds, <= ceil(log2 n) */
+  uint32_t slices;           /* candidate slices every round's sweep ran with */
+  uint32_t query_tiles;
+  uint32_t reserved0;        /* 0 */
+  uint64_t components_after_first_round;
+  double   ms_total;         /* host wall time of the call */
+  uint64_t reserved[1];      /* 0 */
+} ghs_emst_result_t;
+size_t ghs_emst_workspace_bytes(uint32_t n, uint32_t dim, uint32_t slices);   /* host only, no GPU needed */
+int ghs_emst_device(uint32_t n, uint32_t dim, const float *d_x /* n*dim, row-major */,
+                    const float *d_core2 /* n squared core distances, may be NULL */,
+                    uint32_t metric, uint32_t slices /* 0 = auto */,
+                    uint32_t *d_u /* n-1 */, uint32_t *d_v /* n-1 */, float *d_w /* n-1 */,
+                    void *d_workspace, size_t workspace_bytes, void *stream, ghs_emst_result_t *result);
+/* the same for host arrays (copy in, run, copy out on the default stream, slices = auto); the argument
+ * errors above except the 16-byte alignment and the workspace, then GHS_E_NODEVICE without a GPU */
+int ghs_emst_host(uint32_t n, uint32_t dim, const float *x, const float *core2 /* may be NULL */, uint32_t metric,
+                  uint32_t *u, uint32_t *v, float *w, ghs_emst_result_t *result);
+/* the rounds of the calling thread's last ghs_emst_device: *rounds = their number, components[r] = the
+ * components left after round r, scan_ms[r] = the HIP-event time of round r's sweep (0 unless the call ran
+ * after ghs_emst_rounds(1, ...): `enable` takes effect for the next call); at most `capacity` entries are
+ * written, any pointer may be NULL; diagnostic */
+int ghs_emst_rounds(int enable, uint32_t capacity, uint32_t *components, double *scan_ms, uint32_t *rounds);
+
 /* ---- stepwise solver (multi-GPU: one process per GPU, RCCL all-reduce between steps) ------
  * Replaces the per-rank protocol loop of ghs_implementation_mpi.py:673-748 and its
  * collectives (:907 bcast, :929 Barrier, :766 gather). Every rank holds the replicated
